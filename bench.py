@@ -13,6 +13,10 @@ of distinct batches cycled every step; the reference's CPU JPEG decode is not pa
 
 Timing: W untimed warm-up steps; then barrier + device sync, K timed steps, barrier + device sync;
 elapsed = MAX over ranks.  value = N * per_gpu_batch * K / elapsed (weak scaling).
+
+A plain run does only that: set up, warm up, time the K steps, print the one JSON result line
+(``ms_per_step`` = 1000 * elapsed / K).  ``--dump-outputs DIR`` also writes what the last timed step
+computed as ``DIR/<name>.npy``; ``--full`` is the switch for measurements beyond the headline figure.
 """
 from __future__ import annotations
 
@@ -94,7 +98,49 @@ def parse():
     ap.add_argument("--infer", action="store_true",
                     help="inference throughput instead of training: eval-mode forward to the probability map "
                          "(BatchNorm folded into the convs), no loss/backward/optimizer")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): the loss it returned and the parameters and gradients it left (--infer: the "
+                         "probability map and its mean); at most 64 MB in all, larger arrays as a fixed seeded "
+                         "sample.  The inputs depend on the arguments alone, so two builds can be compared")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure.  A plain run sets up, warms up, "
+                         "times --steps steps and prints the result line; anything that takes steps of its own "
+                         "belongs behind this switch (today there is none: --comm-probe, --timing-ablation and "
+                         "the other configurations are explicit options of their own)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 63_000_000     # all dumped arrays together stay under 64 MB
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _dump_outputs(path: str, arrays: dict) -> dict:
+    """Write ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32 (float64 stays float64).  The byte
+    budget is shared smallest array first: one that fits an equal share of what is left is written whole, a
+    larger one is cut to a sorted sample of its flat indices drawn from a fixed-seed generator (the same
+    from run to run, and the same positions for arrays of one length)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    todo = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    written = {}
+    for k, (name, t) in enumerate(todo):
+        t = t.detach().reshape(-1)
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dt == torch.float64 else 4
+        cap = left // (len(todo) - k) // item
+        n = t.numel()
+        if n > cap:
+            gen = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randint(0, n, (cap,), generator=gen).sort().values
+            t = t[idx.to(t.device)]
+        left -= t.numel() * item
+        np.save(os.path.join(path, name + ".npy"), t.to(dt).cpu().numpy())
+        written[name] = {"numel": n, "saved": int(t.numel())}
+    return written
 
 
 def _heartbeat(period: float = 60.0):
@@ -218,10 +264,15 @@ def main():
         assert not mp and world == 1, "--infer: single device"
         strat.model.eval()
 
+    last = {}             # --dump-outputs: the probability map of the latest --infer step
+
     def step(i):
         x, t = pool[i % len(pool)]
         if a.infer:
             with torch.no_grad():
+                if a.dump_outputs:
+                    last["probs"] = strat.compute.probs(x)
+                    return last["probs"].mean()
                 return strat.compute.probs(x).mean()
         return graphed(x, t) if graphed is not None else strat.train_step(x, t)
 
@@ -269,6 +320,20 @@ def main():
         dist.broadcast(lt, src=strat.pipe.head_rank)
         loss = lt
     final_loss = float(loss.item()) if loss is not None else float("nan")
+    dumped = None
+    if a.dump_outputs and rank == 0:      # before anything below runs further steps
+        arrays = {}
+        if loss is not None:
+            arrays["probs_mean" if a.infer else "loss"] = loss
+        if a.infer:
+            arrays["probs"] = last["probs"]
+        else:   # what the step left in this rank's flat parameter spaces
+            spaces = strat.spaces()
+            if spaces:
+                dev0 = spaces[0].data.device
+                arrays["params"] = torch.cat([sp.data.reshape(-1).to(dev0) for sp in spaces])
+                arrays["grads"] = torch.cat([sp.grad.reshape(-1).to(dev0) for sp in spaces])
+        dumped = _dump_outputs(a.dump_outputs, arrays)
 
     # dp: every rank trains its own --batch images (weak scaling); mp: the ranks of a pipeline share one
     # batch, each of the --mp-replicas pipelines trains its own
@@ -327,6 +392,10 @@ def main():
         # the run's non-default kernel switches (ops/config.py; empty = the shipped dispatch)
         "kernel_config": {k: v for k, v in K.CFG.non_default().items()},
     }
+    if a.full:
+        out["full"] = True
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if ablate:
         out["INVALID_timing_ablation"] = ablate
     if dp1:

@@ -341,6 +341,23 @@ def _bench(extra, timeout=300):
     return json.loads(lines[0])
 
 
+def test_bench_dump_outputs_of_the_last_timed_step(hip_lib, tmp_path):
+    """``--dump-outputs DIR`` (here with ``--full``, which a plain run's fields must survive): the loss the
+    last timed step returned and the flat parameters / gradients it left, float32, one entry each."""
+    import numpy as np
+    d = tmp_path / "dump"
+    out = _bench(["--batch", "4", "--img", "128", "--full", "--dump-outputs", str(d)])
+    assert out["steps"] == 3 and out["full"] is True
+    assert abs(out["value"] - 4 * 1000.0 / out["ms_per_step"]) < 0.02 * out["value"]
+    assert sorted(p.name for p in d.iterdir()) == ["grads.npy", "loss.npy", "params.npy"]
+    loss, params, grads = (np.load(d / f"{n}.npy") for n in ("loss", "params", "grads"))
+    assert loss.dtype == params.dtype == grads.dtype == np.float32
+    assert loss.shape == (1,) and abs(float(loss[0]) - out["final_loss"]) <= 1e-5
+    assert params.shape == grads.shape == (7760097,)            # the reference UNet, whole (under the sampling cap)
+    assert out["dumped_outputs"]["params"] == {"numel": 7760097, "saved": 7760097}
+    assert np.isfinite(params).all() and np.isfinite(grads).all() and np.abs(grads).max() > 0
+
+
 def test_bench_dp1proc_replicas_share_one_gpu(hip_lib):
     """VERDICT r5 #3a: ``-t DP`` has a bench path (DPStrategy, one process, a host thread per replica); on one
     GPU its replicas share cuda:0 (host-issue rehearsal, Python-sum reduction instead of the RCCL clique)."""
