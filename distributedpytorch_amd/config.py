@@ -38,6 +38,8 @@ class TrainConfig:
     synthetic_len: int = 5088                        # Carvana's size (train_hq: 5,088 images)
     device_data: bool = True                         # synthetic data rendered once into HBM (no DataLoader/H2D)
     data_dir: str = "./data"
+    device_folder_data: bool = False                 # --data-dir set resized once on the GPU and kept in HBM
+    augment: str = "none"                            # none | hflip (resident folder data only)
     out_dir: str = "."
     device: Optional[str] = None
     stages: int = 2                                  # pipeline stages for -t MP
@@ -95,6 +97,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--host-data", dest="device_data", action="store_false",
                    help="synthetic data through the CPU Dataset/DataLoader + H2D path instead of HBM-resident")
     p.add_argument("--data-dir", type=str, default="./data")
+    p.add_argument("--device-folder-data", action="store_true",
+                   help="--data-dir on a GPU: decode every file once, resize it on the GPU (PIL-exact HIP kernels) "
+                        "and keep the set in HBM as uint8; batches are gathered on the device (on a CPU "
+                        "device the same dataset holds PIL's results). --num-workers = decode threads "
+                        "(0: min(8, cores))")
+    p.add_argument("--augment", choices=["none", "hflip"], default="none",
+                   help="training augmentation of the resident folder data (needs --device-folder-data): hflip = "
+                        "mirror image and mask where a hash of (seed, epoch, item) is odd")
     p.add_argument("--out-dir", type=str, default=".")
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--stages", type=int, default=2)
@@ -142,13 +152,17 @@ def parse_args(argv=None) -> TrainConfig:
     a = build_parser().parse_args(argv)
     if a.train_method not in METHODS:
         raise SystemExit(f"unknown --train-method {a.train_method!r}; choose from {METHODS}")
+    if a.augment != "none" and not a.device_folder_data:
+        raise SystemExit(f"--augment {a.augment} needs --device-folder-data: the augmentation runs in the "
+                         "resident folder dataset's batch kernel, the host DataLoader path has none")
     size = a.img_size
     img_size = (size[0], size[0]) if len(size) == 1 else (size[0], size[1])
     cfg = TrainConfig(
         train_method=a.train_method, val=a.val, load=a.load, epochs=a.epochs, lr=a.lr,
         batch_size=a.batch_size, checkpoint=a.checkpoint, seed=a.seed, img_size=img_size,
         dtype=a.dtype, backend=a.backend, model=a.model, synthetic=a.synthetic,
-        synthetic_len=a.synthetic_len, device_data=a.device_data, data_dir=a.data_dir, out_dir=a.out_dir, device=a.device,
+        synthetic_len=a.synthetic_len, device_data=a.device_data, data_dir=a.data_dir,
+        device_folder_data=a.device_folder_data, augment=a.augment, out_dir=a.out_dir, device=a.device,
         stages=a.stages, microbatches=a.microbatches, mp_cut=a.mp_cut, mp_replicas=a.mp_replicas, bucket_mb=a.bucket_mb,
         grad_comm_dtype=a.grad_comm_dtype,
         comm_overlap=a.comm_overlap, global_dice=a.global_dice,

@@ -7,9 +7,11 @@ from .synthetic import SyntheticSegmentation, synthetic_batch
 from .folder import BasicDataset, CarvanaDataset
 from .loaders import split_dataset, build_loaders, DeviceBatcher
 from .device import DeviceSyntheticSegmentation, DeviceLoader, device_loaders
+from .device_folder import DeviceFolderDataset, DeviceFolderLoader, device_folder_loaders
 
 __all__ = [
     "SyntheticSegmentation", "synthetic_batch", "BasicDataset", "CarvanaDataset",
     "split_dataset", "build_loaders", "DeviceBatcher",
     "DeviceSyntheticSegmentation", "DeviceLoader", "device_loaders",
+    "DeviceFolderDataset", "DeviceFolderLoader", "device_folder_loaders",
 ]

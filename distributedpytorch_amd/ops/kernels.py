@@ -1499,3 +1499,182 @@ def cu_masked_stream(device, reserve: int) -> torch.cuda.ExternalStream:
     s = torch.cuda.ExternalStream(out.value, device=dev)
     s.cus = kept
     return s
+
+
+# ------------------------------------------------------------------------------ data preparation (csrc/data_prep.hip)
+PRECISION_BITS = 22          # PIL Resample.c: fixed-point fraction bits of the 8-bit resampler
+
+
+def _bicubic(x):
+    """PIL's bicubic filter (a = -0.5), evaluated in float64 in Resample.c's operation order."""
+    import numpy as np
+    a = -0.5
+    x = np.abs(x)
+    near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    far = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def bicubic_table(in_size: int, out_size: int):
+    """Per-axis tables of PIL ``Image.resize(BICUBIC)`` for 8-bit images (Resample.c ``precompute_coeffs`` +
+    ``normalize_coeffs_8bpc``): ``bounds int32[out, 2]`` = (first source index, tap count) and
+    ``coefs int32[out, ksize]`` with 22 fractional bits.  One pass is
+    ``clip8(((1 << 21) + sum(pixel * coef)) >> 22)``.  Equal sizes give the identity table (ksize 1,
+    coefficient ``1 << 22``): PIL skips that pass and the table reproduces the input exactly."""
+    import math
+    import numpy as np
+    in_size, out_size = int(in_size), int(out_size)
+    assert in_size > 0 and out_size > 0
+    if in_size == out_size:
+        bounds = np.stack([np.arange(out_size), np.ones(out_size, np.int64)], 1).astype(np.int32)
+        return bounds, np.full((out_size, 1), 1 << PRECISION_BITS, np.int32)
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    ss = 1.0 / filterscale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # (int): truncation, like C
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    k = np.arange(ksize, dtype=np.int64)[None, :]
+    valid = k < n[:, None]
+    w = np.where(valid, _bicubic(((k + xmin[:, None]) - center[:, None] + 0.5) * ss), 0.0)
+    ww = np.zeros(out_size, np.float64)
+    for j in range(ksize):                                                   # sequential sum, like the C loop
+        ww = ww + w[:, j]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    fixed = w * float(1 << PRECISION_BITS)
+    coefs = np.where(w < 0, (fixed - 0.5).astype(np.int64), (fixed + 0.5).astype(np.int64))   # away from zero
+    return np.stack([xmin, n], 1).astype(np.int32), coefs.astype(np.int32)
+
+
+def resample_pass_reference(arr, bounds, coefs, axis: int):
+    """One integer resampling pass over ``axis`` of a uint8 array in numpy (the kernel's arithmetic; tests)."""
+    import numpy as np
+    a = np.moveaxis(np.asarray(arr), axis, 0).astype(np.int64)
+    out = np.empty((bounds.shape[0],) + a.shape[1:], np.uint8)
+    for o in range(bounds.shape[0]):
+        x0, n = int(bounds[o, 0]), int(bounds[o, 1])
+        acc = (1 << (PRECISION_BITS - 1)) + np.tensordot(coefs[o, :n].astype(np.int64), a[x0:x0 + n], axes=(0, 0))
+        out[o] = np.clip(acc >> PRECISION_BITS, 0, 255)
+    return np.moveaxis(out, 0, axis)
+
+
+def resize_bicubic_reference(arr, out_h: int, out_w: int):
+    """PIL ``resize((out_w, out_h), BICUBIC)`` of a uint8 ``[H, W]`` / ``[H, W, C]`` array from the tables:
+    horizontal pass, rounded to uint8, then the vertical pass."""
+    h, w = arr.shape[:2]
+    tmp = resample_pass_reference(arr, *bicubic_table(w, out_w), axis=1)
+    return resample_pass_reference(tmp, *bicubic_table(h, out_h), axis=0)
+
+
+def nearest_table(in_size: int, out_size: int):
+    """Source index per output index of PIL ``NEAREST``, int32: ``min(int((x + 0.5) * in / out), in - 1)``
+    with the coordinate ACCUMULATED as PIL's affine scaler does it (Geometry.c: start at ``scale / 2``, add
+    ``scale`` per step, in float64).  The closed form differs from PIL wherever ``(x + 0.5) * in / out`` is
+    an integer that the running sum lands just below (2 -> 7: index 3 reads source 0, not 1)."""
+    import numpy as np
+    in_size, out_size = int(in_size), int(out_size)
+    assert in_size > 0 and out_size > 0
+    scale = in_size / out_size
+    # np.cumsum adds left to right in float64: the same running sum as the C loop
+    coord = np.cumsum(np.concatenate([[scale * 0.5], np.full(out_size - 1, scale)]))
+    return np.minimum(np.floor(coord).astype(np.int64), in_size - 1).astype(np.int32)
+
+
+_TABLES = {}
+
+
+def _device_table(kind: str, in_size: int, out_size: int, device):
+    """Device copies of the per-axis tables, cached per (kind, in, out, device)."""
+    key = (kind, int(in_size), int(out_size), str(device))
+    t = _TABLES.get(key)
+    if t is None:
+        if kind == "bicubic":
+            b, c = bicubic_table(in_size, out_size)
+            t = (torch.from_numpy(b).to(device), torch.from_numpy(c).to(device), int(c.shape[1]))
+        else:
+            t = torch.from_numpy(nearest_table(in_size, out_size)).to(device)
+        _TABLES[key] = t
+    return t
+
+
+def _u8(t: torch.Tensor, name: str):
+    assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), \
+        f"{name}: need a contiguous cuda uint8 tensor, got {t.dtype} {tuple(t.shape)} on {t.device}"
+
+
+def resize_bicubic_u8(src: torch.Tensor, dst: torch.Tensor) -> bool:
+    """PIL ``resize(BICUBIC)`` of ``src`` uint8 ``[Hs, Ws, C]`` (C in 1, 3; interleaved) into ``dst`` uint8
+    ``[C, Ho, Wo]`` (planar), bit-equal to PIL.  Returns False, without launching, when no tile of the fused
+    kernel fits in LDS (extreme down-scaling): the caller then resizes on the CPU."""
+    _u8(src, "resize_bicubic.src")
+    _u8(dst, "resize_bicubic.dst")
+    assert src.dim() == 3 and dst.dim() == 3 and src.device == dst.device
+    Hs, Ws, C = src.shape
+    assert C in (1, 3) and dst.shape[0] == C, f"resize_bicubic: channels {C} -> {dst.shape[0]}"
+    _, Ho, Wo = dst.shape
+    assert min(Hs, Ws, Ho, Wo) > 0
+    hb, hc, kh = _device_table("bicubic", Ws, Wo, src.device)
+    vb, vc, kv = _device_table("bicubic", Hs, Ho, src.device)
+    err = _lib.lib().dpa_resize_bicubic_u8(_p(src), c_int(Hs), c_int(Ws), c_int(C), _p(dst), c_int(Ho), c_int(Wo),
+                                           _p(hb), _p(hc), c_int(kh), _p(vb), _p(vc), c_int(kv), _stream(src))
+    if int(err) == 1:           # hipErrorInvalidValue after the checks above: the LDS intermediate does not fit
+        return False
+    _check(err, "resize_bicubic_u8")
+    return True
+
+
+def resize_nearest_u8(src: torch.Tensor, dst: torch.Tensor, mask_rule: bool = True,
+                      scratch: Optional[torch.Tensor] = None):
+    """PIL ``resize(NEAREST)`` of a single-channel uint8 ``[Hs, Ws]`` mask into ``dst`` uint8 ``[Ho, Wo]``;
+    with ``mask_rule`` the resized mask then follows ``BasicDataset.preprocess``: maximum > 1 -> value > 127.
+    ``scratch``: one int32 on the device (the mask's maximum), allocated when not given."""
+    _u8(src, "resize_nearest.src")
+    _u8(dst, "resize_nearest.dst")
+    assert src.dim() == 2 and dst.dim() == 2 and src.device == dst.device
+    Hs, Ws = src.shape
+    Ho, Wo = dst.shape
+    assert min(Hs, Ws, Ho, Wo) > 0
+    if scratch is None:
+        scratch = torch.empty(1, dtype=torch.int32, device=src.device)
+    assert scratch.dtype == torch.int32 and scratch.numel() >= 1 and scratch.device == src.device
+    xi = _device_table("nearest", Ws, Wo, src.device)
+    yi = _device_table("nearest", Hs, Ho, src.device)
+    _check(_lib.lib().dpa_resize_nearest_u8(_p(src), c_int(Hs), c_int(Ws), _p(dst), c_int(Ho), c_int(Wo), _p(xi), _p(yi),
+                                            _p(scratch), c_int(int(bool(mask_rule))), _stream(src)), "resize_nearest_u8")
+
+
+def unit_table(device) -> torch.Tensor:
+    """``float32(k / 255.0)`` for the 256 byte values, as the host path computes it (float64 division, then
+    float32): ``float32(k) * float32(1 / 255)`` differs for 126 of them."""
+    key = ("unit", str(device))
+    t = _TABLES.get(key)
+    if t is None:
+        t = _TABLES[key] = (torch.arange(256, dtype=torch.float64) / 255.0).to(torch.float32).to(device)
+    return t
+
+
+def batch_gather_u8(images: torch.Tensor, masks: torch.Tensor, idx: torch.Tensor, flip: Optional[torch.Tensor] = None):
+    """One launch for a batch: ``images`` uint8 ``[N, C, H, W]`` and ``masks`` uint8 ``[N, H, W]`` gathered by
+    ``idx`` int64 ``[B]`` (values in [0, N): the caller's contract, an index outside writes nothing), rows
+    mirrored where ``flip`` uint8 ``[B]`` is set -> (float32 ``[B, C, H, W]`` = value / 255,
+    float32 ``[B, 1, H, W]`` = mask value)."""
+    _u8(images, "batch_gather.images")
+    _u8(masks, "batch_gather.masks")
+    assert images.dim() == 4 and masks.dim() == 3 and images.device == masks.device
+    N, C, H, W = images.shape
+    assert tuple(masks.shape) == (N, H, W), f"batch_gather: masks {tuple(masks.shape)} for images {tuple(images.shape)}"
+    assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and idx.device == images.device
+    B = idx.numel()
+    assert B > 0 and N > 0
+    if flip is not None:
+        assert flip.dtype == torch.uint8 and flip.is_contiguous() and tuple(flip.shape) == (B,) \
+            and flip.device == images.device
+    img = torch.empty(B, C, H, W, dtype=torch.float32, device=images.device)
+    tgt = torch.empty(B, 1, H, W, dtype=torch.float32, device=images.device)
+    _check(_lib.lib().dpa_batch_gather_u8(_p(images), _p(masks), _p(idx), _p(flip), _p(unit_table(images.device)),
+                                          _p(img), _p(tgt), c_ll(N), c_int(B), c_int(C), c_int(H), c_int(W),
+                                          _stream(images)), "batch_gather_u8")
+    return img, tgt

@@ -25,6 +25,7 @@ from .compute import loss_from_partials, make_compute, resolve_backend
 from .config import TrainConfig, dist_env, mp_plan
 from .data import CarvanaDataset, SyntheticSegmentation, build_loaders, split_dataset
 from .data.device import DeviceLoader, DeviceSyntheticSegmentation, device_loaders
+from .data.device_folder import DeviceFolderDataset, DeviceFolderLoader, device_folder_loaders
 from .data.loaders import DeviceBatcher
 from .loss import dice_score
 from .models.unet import build_model
@@ -461,6 +462,17 @@ def build_datasets(cfg: TrainConfig, device=None):
         log.info(f"synthetic dataset resident on {device}: {len(ds)} images, {ds.nbytes / 2 ** 30:.2f} GiB")
     elif cfg.synthetic:
         ds = SyntheticSegmentation(cfg.synthetic_len, (H, W), 3, seed=cfg.seed)
+    elif cfg.device_folder_data and device is not None:
+        # every rank / pipeline stage loads the full resized set (data/device_folder.py); on a CPU device the
+        # same class holds PIL's results
+        root = cfg.data_dir
+        t0 = time.perf_counter()
+        ds = DeviceFolderDataset(os.path.join(root, "train_hq"), os.path.join(root, "train_masks"), newsize=(W, H),
+                                 mask_suffix="_mask", device=device, workers=cfg.num_workers)
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize(device)
+        log.info(f"folder dataset resident on {device}: {len(ds)} images, {ds.nbytes / 2 ** 30:.2f} GiB, loaded in "
+                 f"{time.perf_counter() - t0:.1f} s ({ds.cpu_resized} files resized on the CPU)")
     else:
         root = cfg.data_dir
         ds = CarvanaDataset(os.path.join(root, "train_hq"), os.path.join(root, "train_masks"), newsize=(W, H))
@@ -476,7 +488,7 @@ def _base_dataset(ds):
 def _batches(loader, device):
     """(images, targets) on the device: HBM-resident loaders yield them directly; host loaders go
     through the prefetching H2D batcher."""
-    return loader if isinstance(loader, DeviceLoader) else DeviceBatcher(loader, device)
+    return loader if isinstance(loader, (DeviceLoader, DeviceFolderLoader)) else DeviceBatcher(loader, device)
 
 
 def _setup_logging(cfg, rank):
@@ -529,6 +541,10 @@ def train(cfg: TrainConfig):
         train_loader, val_loader, sampler = device_loaders(
             train_set, val_set, cfg.batch_size, rank=dp_rank, world_size=dp_ranks, seed=cfg.seed,
             drop_last=strat.name in ("MP",))
+    elif isinstance(_base_dataset(train_set), DeviceFolderDataset):
+        train_loader, val_loader, sampler = device_folder_loaders(
+            train_set, val_set, cfg.batch_size, rank=dp_rank, world_size=dp_ranks, seed=cfg.seed,
+            drop_last=strat.name in ("MP",), augment=cfg.augment)
     else:
         train_loader, val_loader, sampler = build_loaders(
             train_set, val_set, cfg.batch_size, rank=dp_rank, world_size=dp_ranks, num_workers=cfg.num_workers,

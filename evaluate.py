@@ -51,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--synthetic-len", type=int, default=64)
     ap.add_argument("--data-dir", default="./data")
+    ap.add_argument("--device-folder-data", action="store_true",
+                    help="--data-dir resized once on the GPU and kept in HBM (as train.py --device-folder-data)")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--model", default="unet")
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
@@ -66,9 +68,16 @@ def main(argv=None):
     dev = "cuda:0" if torch.cuda.is_available() else "cpu"
     dtype = a.dtype or ("bf16" if dev != "cpu" else "fp32")
     cfg = TrainConfig(backend=a.backend, img_size=(H, W), dtype=dtype, synthetic=a.synthetic,
-                      synthetic_len=a.synthetic_len, seed=a.seed, val=a.validation, data_dir=a.data_dir)
+                      synthetic_len=a.synthetic_len, seed=a.seed, val=a.validation, data_dir=a.data_dir,
+                      device_folder_data=a.device_folder_data)
     strat = SingleDevice(cfg, model, dev)
-    if a.synthetic and dev != "cpu":
+    if a.device_folder_data and not a.synthetic and dev != "cpu":
+        # the SAME validation images train.py --device-folder-data held out, resized on the GPU
+        from distributedpytorch_amd.trainer import build_datasets
+        from distributedpytorch_amd.data.device_folder import device_folder_loaders
+        train_set, val_set = build_datasets(cfg, dev)
+        _, val_loader, _ = device_folder_loaders(train_set, val_set, a.batch_size)
+    elif a.synthetic and dev != "cpu":
         # the SAME validation images train.py --synthetic held out (GPU-resident set, seed, split)
         from distributedpytorch_amd.trainer import build_datasets
         from distributedpytorch_amd.data.device import device_loaders
