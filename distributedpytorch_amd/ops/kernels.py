@@ -1678,3 +1678,135 @@ def batch_gather_u8(images: torch.Tensor, masks: torch.Tensor, idx: torch.Tensor
                                           _p(img), _p(tgt), c_ll(N), c_int(B), c_int(C), c_int(H), c_int(W),
                                           _stream(images)), "batch_gather_u8")
     return img, tgt
+
+
+# ------------------------------------------------------------------------------ prediction post-processing (csrc/predict_post.hip)
+PREDICT_KMAX = 9             # taps per axis dpa_prob_to_mask_u8 accepts (down-scaling up to 4x)
+
+
+def bilinear_table(in_size: int, out_size: int):
+    """Per-axis tables of PIL ``Image.resize(BILINEAR)`` for mode ``F`` images (Resample.c ``precompute_coeffs``
+    with the triangle filter; the 32bpc passes use the float64 coefficients as they are): ``bounds int32[out, 2]``
+    = (first source index, tap count) and ``coefs float64[out, ksize]``.  One pass is ``ss = 0.0``,
+    ``ss += float64(pixel) * coef`` in tap order, rounded to float32.  Equal sizes give the identity table
+    (ksize 1, coefficient 1.0): PIL skips that pass and the table reproduces the input exactly."""
+    import math
+    import numpy as np
+    in_size, out_size = int(in_size), int(out_size)
+    assert in_size > 0 and out_size > 0
+    if in_size == out_size:
+        bounds = np.stack([np.arange(out_size), np.ones(out_size, np.int64)], 1).astype(np.int32)
+        return bounds, np.ones((out_size, 1), np.float64)
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    ss = 1.0 / filterscale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # (int): truncation, like C
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    k = np.arange(ksize, dtype=np.int64)[None, :]
+    x = np.abs(((k + xmin[:, None]) - center[:, None] + 0.5) * ss)
+    w = np.where((k < n[:, None]) & (x < 1.0), 1.0 - x, 0.0)                 # the triangle filter
+    ww = np.zeros(out_size, np.float64)
+    for j in range(ksize):                                                   # sequential sum, like the C loop
+        ww = ww + w[:, j]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    return np.stack([xmin, n], 1).astype(np.int32), np.ascontiguousarray(w)
+
+
+def _bilinear_pass_reference(a, bounds, coefs, axis: int):
+    import numpy as np
+    a = np.moveaxis(np.asarray(a, np.float32), axis, 0)
+    x0, n = bounds[:, 0].astype(np.int64), bounds[:, 1]
+    shape = (-1,) + (1,) * (a.ndim - 1)
+    ss = np.zeros((bounds.shape[0],) + a.shape[1:], np.float64)
+    for j in range(coefs.shape[1]):                                          # tap order; a multiply, then an add
+        tap = a[np.minimum(x0 + j, a.shape[0] - 1)].astype(np.float64) * coefs[:, j].reshape(shape)
+        ss = np.where((j < n).reshape(shape), ss + tap, ss)
+    return np.moveaxis(ss.astype(np.float32), 0, axis)
+
+
+def resize_bilinear_reference(p, out_h: int, out_w: int):
+    """PIL ``Image.fromarray(p, mode="F").resize((out_w, out_h), BILINEAR)`` of a float32 ``[h, w]`` array from
+    the tables, in numpy (the kernel's arithmetic): horizontal pass, rounded to float32, then the vertical pass;
+    a pass between equal sizes is skipped."""
+    import numpy as np
+    p = np.asarray(p, np.float32)
+    h, w = p.shape
+    if w != out_w:
+        p = _bilinear_pass_reference(p, *bilinear_table(w, out_w), axis=1)
+    if h != out_h:
+        p = _bilinear_pass_reference(p, *bilinear_table(h, out_h), axis=0)
+    return p
+
+
+def _bilinear_device_table(in_size: int, out_size: int, device):
+    key = ("bilinear", int(in_size), int(out_size), str(device))
+    t = _TABLES.get(key)
+    if t is None:
+        b, c = bilinear_table(in_size, out_size)
+        t = _TABLES[key] = (torch.from_numpy(b).to(device), torch.from_numpy(c).to(device), int(c.shape[1]))
+    return t
+
+
+def prob_to_mask_u8(probs: torch.Tensor, dst: torch.Tensor, threshold: float = 0.5, value: int = 255) -> bool:
+    """``probs`` float32 ``[B, h, w]`` -> ``dst`` uint8 ``[B, H, W]`` = ``value`` where the PIL-bilinear resize of
+    the probabilities (mode ``F``, bit-equal) exceeds ``float32(threshold)``, else 0; one launch for the batch.
+    Returns False, without launching, when an axis is down-scaled by more than 4x (ksize > 9): the caller
+    then resizes on the host."""
+    _u8(dst, "prob_to_mask.dst")
+    assert probs.dtype == torch.float32 and probs.is_cuda and probs.is_contiguous(), \
+        f"prob_to_mask.probs: need a contiguous cuda float32 tensor, got {probs.dtype} {tuple(probs.shape)} on {probs.device}"
+    assert probs.dim() == 3 and dst.dim() == 3 and probs.device == dst.device and probs.shape[0] == dst.shape[0]
+    B, h, w = probs.shape
+    _, H, W = dst.shape
+    assert min(B, h, w, H, W) > 0 and 0 <= int(value) <= 255
+    hb, hc, kh = _bilinear_device_table(w, W, probs.device)
+    vb, vc, kv = _bilinear_device_table(h, H, probs.device)
+    if kh > PREDICT_KMAX or kv > PREDICT_KMAX:
+        return False
+    err = _lib.lib().dpa_prob_to_mask_u8(_p(probs), c_int(B), c_int(h), c_int(w), _p(dst), c_int(H), c_int(W),
+                                         _p(hb), _p(hc), c_int(kh), _p(vb), _p(vc), c_int(kv),
+                                         ctypes.c_float(float(threshold)), c_int(int(value)), _stream(probs))
+    _check(err, "prob_to_mask_u8")
+    return True
+
+
+def rle_reference(mask):
+    """Run-length list of a mask ``[H, W]`` in numpy: the maximal runs of non-zero values in the row-major
+    flattened image as int32 ``[n, 2]`` = (start, length), start 1-indexed, ascending (the Carvana encoding)."""
+    import numpy as np
+    nz = np.concatenate([[False], np.asarray(mask).reshape(-1) != 0, [False]])
+    edges = np.flatnonzero(nz[1:] != nz[:-1]).reshape(-1, 2)                 # start, end (exclusive), 0-indexed
+    return np.stack([edges[:, 0] + 1, edges[:, 1] - edges[:, 0]], 1).astype(np.int32)
+
+
+def rle_decode(runs, H: int, W: int):
+    """The boolean mask ``[H, W]`` of a (start, length) list (1-indexed starts): the inverse of ``rle_reference``."""
+    import numpy as np
+    m = np.zeros(int(H) * int(W), np.bool_)
+    for s, n in np.asarray(runs, np.int64).reshape(-1, 2):
+        assert 1 <= s and n >= 1 and s - 1 + n <= m.size, f"run ({s}, {n}) outside a {H}x{W} image"
+        m[s - 1:s - 1 + n] = True
+    return m.reshape(int(H), int(W))
+
+
+def mask_rle(masks: torch.Tensor, cap: int):
+    """Run-length lists of ``masks`` uint8 ``[B, H, W]`` on the device -> (``runs`` int32 ``[B, cap, 2]`` =
+    (start, length) as ``rle_reference``, ``counts`` int32 ``[B]``).  ``counts[b]`` is the true number of runs;
+    where it exceeds ``cap`` only the first ``cap`` runs were written and the caller encodes on the host.
+    Entries of ``runs`` behind ``min(counts[b], cap)`` are not written."""
+    _u8(masks, "mask_rle.masks")
+    assert masks.dim() == 3 and min(masks.shape) > 0 and int(cap) >= 1
+    B, H, W = masks.shape
+    assert H * W < 2 ** 31, f"mask_rle: {H}x{W} positions do not fit in int32"
+    L = _lib.lib()
+    tiles = int(L.dpa_mask_rle_tiles(c_int(H), c_int(W)))
+    runs = torch.empty(B, int(cap), 2, dtype=torch.int32, device=masks.device)
+    counts = torch.empty(B, dtype=torch.int32, device=masks.device)
+    work = torch.empty(B * tiles, dtype=torch.int32, device=masks.device)
+    _check(L.dpa_mask_rle(_p(masks), c_int(B), c_int(H), c_int(W), _p(runs), c_int(int(cap)), _p(counts), _p(work),
+                          c_ll(work.numel()), _stream(masks)), "mask_rle")
+    return runs, counts
