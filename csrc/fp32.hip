@@ -849,7 +849,7 @@ __global__ __launch_bounds__(256) void head_f32_kernel(const float* __restrict__
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long)gridDim.x * blockDim.x) {
     float z = b[0];
     for (int c = 0; c < C; ++c) z = fmaf(w[c], y[i * C + c], z);
-    const float p = 1.f / (1.f + expf(-z));
+    const float p = 1.f / (1.f + exp_hw(-z));
     if (probs) probs[i] = p;
     if (t) {
       const float tt = t[i];
@@ -895,7 +895,7 @@ __global__ __launch_bounds__(256) void head_f32_vec_kernel(const float* __restri
     for (int o = L / 2; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
     z += bb;
     if (sub == 0) {
-      const float p = 1.f / (1.f + expf(-z));
+      const float p = 1.f / (1.f + exp_hw(-z));
       if (probs) probs[i] = p;
       if (t) {
         const float tt = t[i];
@@ -946,7 +946,7 @@ __global__ __launch_bounds__(256) void head_bwd_f32_vec_kernel(const float* __re
 #pragma unroll
     for (int o = L / 2; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
     z += bb;
-    const float p = 1.f / (1.f + expf(-z));
+    const float p = 1.f / (1.f + exp_hw(-z));
     const float tt = t[i];
     const float dz = head_dz(p, tt, tt == 1.f ? 1.f : 0.f, d0, d1, d2);
     f32x4v o = dz * wv;

@@ -13,6 +13,13 @@
 // pixel rows x G groups of 8 channels, consecutive rows = consecutive pixels, so a block streams a
 // contiguous R*C*2-byte span when G*8 == C); bn_*_finalize_kernel sums the rows in a fixed order,
 // one block per channel.  The same pair computes the backward sums (sum g, sum g*(z-mean)).
+//
+// The forward sums are taken about a per-channel pivot k_c = z[pixel 0][c]: s = sum (z - k), q = sum (z - k)^2,
+// mean = k + s/P, var = q/P - (s/P)^2.  With raw sums the variance of a channel with |mean| >> sigma is the
+// difference of two nearly equal fp32 numbers (relative error ~ 2^-24 (mean/sigma)^2 sqrt(P)); about the pivot
+// the sums are of order sigma and a constant channel gives var = 0 exactly.  The pivot travels from the partial
+// pass to the finalize in saved[c], which the finalize then overwrites with the mean.  Slabs written by conv
+// epilogues (slab_rows > 0) hold raw sums (pivot 0).
 #include "common.h"
 
 #include "conv_args.h"   // pool_code
@@ -23,7 +30,7 @@
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const bf16_t* __restrict__ a, int lda, const bf16_t* __restrict__ z,
                                                          int ldz, const float* __restrict__ saved, long P, int C, int G,
-                                                         float* __restrict__ slab) {
+                                                         float* __restrict__ slab, float* __restrict__ pivot) {
   __shared__ float red[256 * 16];
   const int tid = threadIdx.x;
   const int R = 256 / G;
@@ -36,13 +43,26 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const bf16_t* __restric
     q[k] = 0.f;
     mu[k] = MODE ? saved[c0 + k] : 0.f;
   }
+  if (MODE == 0) {   // pivot: the first pixel's value (handed to the finalize in pivot = saved[0..C))
+    const uint4 u = *reinterpret_cast<const uint4*>(a + c0);
+    const unsigned* pu = &u.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      mu[2 * e] = lo_bf(pu[e]);
+      mu[2 * e + 1] = hi_bf(pu[e]);
+    }
+    if (blockIdx.x == 0 && r == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) pivot[c0 + k] = mu[k];
+    }
+  }
   for (long p = (long)blockIdx.x * R + r; p < P; p += (long)gridDim.x * R) {
     const uint4 u = *reinterpret_cast<const uint4*>(a + p * lda + c0);
     const unsigned* pu = &u.x;
     if (MODE == 0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float v0 = lo_bf(pu[e]), v1 = hi_bf(pu[e]);
+        const float v0 = lo_bf(pu[e]) - mu[2 * e], v1 = hi_bf(pu[e]) - mu[2 * e + 1];
         s[2 * e] += v0; q[2 * e] = fmaf(v0, v0, q[2 * e]);
         s[2 * e + 1] += v1; q[2 * e + 1] = fmaf(v1, v1, q[2 * e + 1]);
       }
@@ -107,11 +127,12 @@ DPA_API int dpa_slab_fold(const float* in, int rows, int K, int nout, float* out
 
 // Forward coefficients y = z*coef[c] + coef[C+c].  train: batch statistics (saved = mean, invstd
 // for the backward; running stats updated in place); eval (slab == null): running statistics.
+// pivoted: the slab holds sums about the pivot the partial pass left in saved[c] (else raw sums).
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ slab, int nblk, int C, long P,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float eps, float momentum, float* __restrict__ rmean,
                                                           float* __restrict__ rvar, float* __restrict__ coef,
-                                                          float* __restrict__ saved) {
+                                                          float* __restrict__ saved, int pivoted) {
   __shared__ float red[4];
   const int c = blockIdx.x;
   float mean, var;
@@ -121,7 +142,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     const double m = (double)s / (double)P;
     double v = (double)q / (double)P - m * m;
     if (v < 0.0) v = 0.0;
-    mean = (float)m;
+    mean = (float)(pivoted ? (double)saved[c] + m : m);
     var = (float)v;
   } else {
     mean = rmean[c];
@@ -148,7 +169,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
 // and dgamma += sum g*xhat, dbeta += sum g (accumulated into the flat fp32 gradient buffer).
 // gy_mode (slab from the dgrad epilogue, csrc/halo.hip EPI 5): the second column is sum g*y with
 // y = relu(gamma xhat + beta) the BN output; g vanishes where y == 0, elsewhere xhat = (y - beta)/gamma,
-// so sum g*xhat = (sum g*y - beta sum g) / gamma.
+// so sum g*xhat = (sum g*y - beta sum g) / gamma.  gamma == 0: y = relu(beta) no longer carries xhat, the sum
+// cannot be recovered and that channel's dgamma contribution is 0 (dz = 0 either way).
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __restrict__ slab, int nblk, int C, long P,
                                                               const float* __restrict__ gamma, const float* __restrict__ saved,
                                                               float* __restrict__ coef3, float* __restrict__ dgamma,
@@ -160,7 +182,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
   slab_pair(slab, nblk, C, c, red, sg, sgz);
   if (threadIdx.x != 0) return;
   const float mean = saved[c], invstd = saved[C + c];
-  const float sgx = gy_mode ? (sgz - beta[c] * sg) / gamma[c] : sgz * invstd;
+  const float sgx = gy_mode ? (gamma[c] != 0.f ? (sgz - beta[c] * sg) / gamma[c] : 0.f) : sgz * invstd;
   if (dgamma) dgamma[c] += sgx;
   if (dbeta) dbeta[c] += sg;
   const float sc = gamma[c] * invstd;
@@ -313,12 +335,12 @@ DPA_API int dpa_bn_fwd(const bf16_t* z, int ldz, bf16_t* y, int ldy, long long P
     // slab_rows > 0: the producing conv already wrote the partial sums (igemm_stream EPI 4)
     if (slab_rows <= 0)
       hipLaunchKernelGGL(bn_partial_kernel<0>, grid, dim3(256), 0, st, z, ldz, (const bf16_t*)nullptr, 0,
-                         (const float*)nullptr, (long)P, C, G, slab);
+                         (const float*)nullptr, (long)P, C, G, slab, saved);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, slab, slab_rows > 0 ? slab_rows : (int)grid.x, C,
-                       (long)P, gamma, beta, eps, momentum, rmean, rvar, coef, saved);
+                       (long)P, gamma, beta, eps, momentum, rmean, rvar, coef, saved, slab_rows > 0 ? 0 : 1);
   } else {
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, (const float*)nullptr, 0, C, (long)P, gamma, beta, eps,
-                       momentum, rmean, rvar, coef, saved);
+                       momentum, rmean, rvar, coef, saved, 0);
   }
   // coefficients only (y == pool == null): the consumer applies the BN + ReLU on load (IgemmArgs::xbn);
   // y == null with pool: only the pooled tensor and its window codes (the consumers of y read z on load)
@@ -345,7 +367,8 @@ DPA_API int dpa_bn_bwd_coef(const bf16_t* g, int ldg, const bf16_t* z, int ldz, 
   if (!bn_shape(P, C, G, grid) || (ldg & 7) || (ldz & 7)) return (int)hipErrorInvalidValue;
   if (slab_rows > 0 && beta == nullptr) return (int)hipErrorInvalidValue;
   if (slab_rows <= 0)
-    hipLaunchKernelGGL(bn_partial_kernel<1>, grid, dim3(256), 0, st, g, ldg, z, ldz, saved, (long)P, C, G, slab);
+    hipLaunchKernelGGL(bn_partial_kernel<1>, grid, dim3(256), 0, st, g, ldg, z, ldz, saved, (long)P, C, G, slab,
+                       (float*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, slab, slab_rows > 0 ? slab_rows : (int)grid.x, C,
                      (long)P, gamma, saved, coef3, dgamma, dbeta, beta, slab_rows > 0 ? 1 : 0);
   return (int)hipGetLastError();
@@ -362,7 +385,8 @@ DPA_API int dpa_bn_bwd(const bf16_t* g, int ldg, const bf16_t* z, int ldz, bf16_
   // slab_rows > 0: (sum g, sum g*y) partials already written by the producing dgrad (needs beta)
   if (slab_rows > 0 && beta == nullptr) return (int)hipErrorInvalidValue;
   if (slab_rows <= 0)
-    hipLaunchKernelGGL(bn_partial_kernel<1>, grid, dim3(256), 0, st, g, ldg, z, ldz, saved, (long)P, C, G, slab);
+    hipLaunchKernelGGL(bn_partial_kernel<1>, grid, dim3(256), 0, st, g, ldg, z, ldz, saved, (long)P, C, G, slab,
+                       (float*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, slab, slab_rows > 0 ? slab_rows : (int)grid.x, C,
                      (long)P, gamma, saved, coef3, dgamma, dbeta, beta, slab_rows > 0 ? 1 : 0);
   const long tot = (long)P * (C / 8);
@@ -481,7 +505,7 @@ DPA_API int dpa_up2_bwd(const bf16_t* g, int ldg, bf16_t* dx, int lddx, int N, i
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_partial_f32_kernel(const float* __restrict__ a, int lda, const float* __restrict__ z,
                                                              int ldz, const float* __restrict__ saved, long P, int C, int G,
-                                                             float* __restrict__ slab) {
+                                                             float* __restrict__ slab, float* __restrict__ pivot) {
   __shared__ float red[256 * 8];
   const int tid = threadIdx.x;
   const int R = 256 / G;
@@ -494,14 +518,23 @@ __global__ __launch_bounds__(256) void bn_partial_f32_kernel(const float* __rest
     q[k] = 0.f;
     mu[k] = MODE ? saved[c0 + k] : 0.f;
   }
+  if (MODE == 0) {   // pivot: the first pixel's value (handed to the finalize in pivot = saved[0..C))
+    const float4 u = *reinterpret_cast<const float4*>(a + c0);
+    mu[0] = u.x; mu[1] = u.y; mu[2] = u.z; mu[3] = u.w;
+    if (blockIdx.x == 0 && r == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pivot[c0 + k] = mu[k];
+    }
+  }
   for (long p = (long)blockIdx.x * R + r; p < P; p += (long)gridDim.x * R) {
     const float4 u = *reinterpret_cast<const float4*>(a + p * lda + c0);
     const float v[4] = {u.x, u.y, u.z, u.w};
     if (MODE == 0) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        s[k] += v[k];
-        q[k] = fmaf(v[k], v[k], q[k]);
+        const float d = v[k] - mu[k];
+        s[k] += d;
+        q[k] = fmaf(d, d, q[k]);
       }
     } else {
       const float4 w = *reinterpret_cast<const float4*>(z + p * ldz + c0);
@@ -596,12 +629,12 @@ DPA_API int dpa_bn_fwd_f32(const float* z, int ldz, float* y, int ldy, long long
   if (!bn_shape_f32(P, C, G, grid) || (ldz & 3) || (ldy & 3)) return (int)hipErrorInvalidValue;
   if (train) {
     hipLaunchKernelGGL(bn_partial_f32_kernel<0>, grid, dim3(256), 0, st, z, ldz, (const float*)nullptr, 0,
-                       (const float*)nullptr, (long)P, C, G, slab);
+                       (const float*)nullptr, (long)P, C, G, slab, saved);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, slab, (int)grid.x, C, (long)P, gamma, beta, eps,
-                       momentum, rmean, rvar, coef, saved);
+                       momentum, rmean, rvar, coef, saved, 1);
   } else {
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, (const float*)nullptr, 0, C, (long)P, gamma, beta, eps,
-                       momentum, rmean, rvar, coef, saved);
+                       momentum, rmean, rvar, coef, saved, 0);
   }
   const long tot = (long)P * (C / 4);
   hipLaunchKernelGGL(bn_apply_f32_kernel, dim3(dpa_grid(tot, 256, 16384)), dim3(256), 0, st, z, ldz, y, ldy, coef, (long)P, C,
@@ -616,7 +649,8 @@ DPA_API int dpa_bn_bwd_f32(const float* g, int ldg, const float* z, int ldz, flo
   int G;
   dim3 grid;
   if (!bn_shape_f32(P, C, G, grid) || (ldg & 3) || (ldz & 3) || (lddz & 3)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(bn_partial_f32_kernel<1>, grid, dim3(256), 0, st, g, ldg, z, ldz, saved, (long)P, C, G, slab);
+  hipLaunchKernelGGL(bn_partial_f32_kernel<1>, grid, dim3(256), 0, st, g, ldg, z, ldz, saved, (long)P, C, G, slab,
+                     (float*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, slab, (int)grid.x, C, (long)P, gamma, saved, coef3,
                      dgamma, dbeta, (const float*)nullptr, 0);
   const long tot = (long)P * (C / 4);

@@ -352,8 +352,10 @@ def _declare_norm():
 def bn_fwd(z: torch.Tensor, bn: torch.nn.BatchNorm2d, train: bool, relu: bool = True,
            y: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """y = relu(BatchNorm2d(z)), NHWC fp32 (csrc/norm_up.hip fp32 forms; torch.nn.BatchNorm2d semantics:
-    biased batch variance to normalise, unbiased for running_var, ``momentum`` update).  Returns (y, saved):
-    saved = [mean, invstd] for :func:`bn_bwd` in training, None in eval (running statistics)."""
+    biased batch variance to normalise, unbiased for running_var, ``momentum`` update -- None: the cumulative
+    average 1 / num_batches_tracked).  Returns (y, saved): saved = [mean, invstd] for :func:`bn_bwd` whenever
+    batch statistics normalise (training, or a layer without running statistics), None in eval with running
+    statistics.  The same host logic as the bf16 binding (``ops.kernels.bn_fwd``)."""
     L = _declare_norm()
     N, H, W, C, ldz = nhwc(z, "bn_fwd_f32.z")
     if y is None:
@@ -361,18 +363,23 @@ def bn_fwd(z: torch.Tensor, bn: torch.nn.BatchNorm2d, train: bool, relu: bool = 
     _, _, _, _, ldy = nhwc(y, "bn_fwd_f32.y")
     P = N * H * W
     rows = L.dpa_bn_slab_rows_f32(P, C)
+    track = bn.track_running_stats and bn.running_mean is not None
+    use_batch = train or not track       # no running statistics: batch statistics in eval too (torch)
     slab = torch.empty(max(rows, 1) * 2 * C, dtype=torch.float32, device=z.device)
     coef = torch.empty(2 * C, dtype=torch.float32, device=z.device)
-    saved = torch.empty(2 * C, dtype=torch.float32, device=z.device) if train else None
-    track = train and bn.track_running_stats and bn.running_mean is not None
-    if train and bn.num_batches_tracked is not None:
+    saved = torch.empty(2 * C, dtype=torch.float32, device=z.device) if use_batch else None
+    if train and track and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    mom = bn.momentum if bn.momentum is not None else 0.1
+    if bn.momentum is not None:
+        mom = bn.momentum
+    else:   # cumulative moving average (torch: momentum = 1 / num_batches_tracked)
+        mom = 1.0 / max(1, int(bn.num_batches_tracked.item())) if track else 0.0
+    # running stats: updated when training, read in eval (use_batch False); null when the layer keeps none
     _check(L.dpa_bn_fwd_f32(_p(z), c_int(ldz), _p(y), c_int(ldy), c_ll(P), c_int(C), _p(bn.weight.detach()),
                             _p(bn.bias.detach()), ctypes.c_float(bn.eps), ctypes.c_float(mom),
-                            _p(bn.running_mean) if (track or not train) else None,
-                            _p(bn.running_var) if (track or not train) else None, _p(slab), _p(coef), _p(saved),
-                            c_int(1 if train else 0), c_int(1 if relu else 0), _st(z)), "bn_fwd_f32")
+                            _p(bn.running_mean) if track else None, _p(bn.running_var) if track else None,
+                            _p(slab), _p(coef), _p(saved), c_int(1 if use_batch else 0), c_int(1 if relu else 0),
+                            _st(z)), "bn_fwd_f32")
     return y, saved
 
 

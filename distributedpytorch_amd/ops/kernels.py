@@ -584,11 +584,7 @@ def _wgrad_up(A, B, *, grid, M, Nc, gw, gb, Nreal):
     _check(L.dpa_wgrad_reduce(_p(slab), None, _p(gw), None, c_int(splits), c_int(4), c_int(Nc), c_int(M), c_int(M),
                               c_int(0), st), "wgrad_reduce(up)")
     if gb is not None:
-        P = N * 4 * h * w
-        nblk = max(1, min(1024, P * (M // 8) // 4096))
-        part = torch.empty(nblk * M, dtype=torch.float32, device=A.device)
-        _check(L.dpa_chan_sum_bf16(_p(A), ctypes.c_longlong(P), c_int(M), c_int(lda), _p(part), c_int(nblk), _p(gb),
-                                   st), "chan_sum_bf16")
+        _chan_sum_bf16(A[..., :M], gb)
 
 
 # deep-layer weight gradients with the input band staged once for all nine taps (csrc/wgrad_band.hip):
@@ -1293,6 +1289,26 @@ def _fold_slab(slab: torch.Tensor, rows: int, K: int, max_rows: int = 512):
     return out, nout
 
 
+def _slab_sum(slab: torch.Tensor, rows: int, K: int) -> torch.Tensor:
+    """Column sums [K] of a slab [rows][K] (one block per column, fixed order: dpa_slab_sum)."""
+    assert slab.dtype == torch.float32 and slab.is_contiguous() and slab.numel() >= rows * K and rows >= 1 and K >= 1
+    out = torch.empty(K, dtype=torch.float32, device=slab.device)
+    _check(_lib.lib().dpa_slab_sum(_p(slab), c_int(rows), c_int(K), _p(out), _stream(slab)), "slab_sum")
+    return out
+
+
+def _chan_sum_bf16(g: torch.Tensor, out: torch.Tensor, nblk: int = 0) -> None:
+    """out[c] += sum over the pixels of NHWC bf16 g (a channel slice allowed; C / 8 divides 256, C <= 2048):
+    ``nblk`` per-block partial rows (0: by size), then the fixed-order column sums (dpa_chan_sum_bf16)."""
+    N, H, W, C, ld = _nhwc(g, "chan_sum.g")
+    _flat_f32(out, C, "chan_sum.out")
+    P = N * H * W
+    nblk = nblk or max(1, min(1024, P * (C // 8) // 4096))
+    part = torch.empty(nblk * C, dtype=torch.float32, device=g.device)
+    _check(_lib.lib().dpa_chan_sum_bf16(_p(g), c_ll(P), c_int(C), c_int(ld), _p(part), c_int(nblk), _p(out),
+                                        _stream(g)), "chan_sum_bf16")
+
+
 def bn_fwd(z: torch.Tensor, y: Optional[torch.Tensor], bn: torch.nn.BatchNorm2d, train: bool, relu: bool = True,
            stats: Optional[list] = None, pool: Optional[torch.Tensor] = None, pcode: Optional[torch.Tensor] = None,
            coef_out: Optional[list] = None):
@@ -1300,6 +1316,11 @@ def bn_fwd(z: torch.Tensor, y: Optional[torch.Tensor], bn: torch.nn.BatchNorm2d,
     running stats updated (torch momentum semantics); returns ``saved`` = [mean, invstd] (fp32 [2C])
     for :func:`bn_bwd`.  Eval: running statistics, returns None.  ``stats`` = (slab, rows) partial
     sums the producing conv already computed (:func:`igemm` ``bn_stats``): no statistics pass.
+    The statistics pass of this function sums about a per-channel pivot (csrc/norm_up.hip) and holds
+    invstd to rtol 1e-3 of the float64 value of the bf16 data at any |mean| / sigma (a constant channel
+    gives exactly 1 / sqrt(eps)); the conv epilogues' slabs carry raw fp32 sums sum z, sum z^2, so the
+    fused-statistics path is specified only up to |mean| / sigma ~ 10 (the variance loses about
+    2^-24 (mean / sigma)^2 sqrt(P) relative).
     ``pool``/``pcode``: also the 2x2 max-pool of y and its window codes, in the same pass (even H, W;
     otherwise a separate :func:`maxpool2`).  ``y=None`` (with ``coef_out``, an empty list): no
     normalise pass at all -- the statistics and running stats update as usual and ``coef_out``
@@ -1360,7 +1381,9 @@ def bn_bwd(g: torch.Tensor, z: torch.Tensor, saved: torch.Tensor, bn: torch.nn.B
            dgamma: Optional[torch.Tensor], dbeta: Optional[torch.Tensor], stats: Optional[list] = None) -> torch.Tensor:
     """dz from g = dL/d(BN output) (ReLU mask already applied); dgamma/dbeta += (fp32 [C]).
     ``stats`` = (slab, rows) of (sum g, sum g*y) from the dgrad that produced g (:func:`igemm`
-    ``bn_stats`` with the BN output as mask): no reduction pass over (g, z)."""
+    ``bn_stats`` with the BN output as mask): no reduction pass over (g, z).  That form recovers
+    sum g*xhat as (sum g*y - beta sum g) / gamma, so it carries the bf16 rounding of y divided by
+    gamma; a channel with gamma == 0 (y = relu(beta) holds no xhat) gets dgamma += 0 and dz = 0."""
     N, H, W, C, ldg = _nhwc(g, "bn_bwd.g")
     Nz, Hz, Wz, Cz, ldz = _nhwc(z, "bn_bwd.z")
     assert (Nz, Hz, Wz, Cz) == (N, H, W, C) and saved.numel() == 2 * C
