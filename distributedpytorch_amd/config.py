@@ -39,7 +39,14 @@ class TrainConfig:
     device_data: bool = True                         # synthetic data rendered once into HBM (no DataLoader/H2D)
     data_dir: str = "./data"
     device_folder_data: bool = False                 # --data-dir set resized once on the GPU and kept in HBM
-    augment: str = "none"                            # none | hflip (resident folder data only)
+    augment: str = "none"                            # none, or hflip / affine / color joined by + (canonical
+                                                     # order; resident folder data only; data/augment.py)
+    aug_scale: Optional[float] = None                # --aug-*: magnitudes of affine (scale, rotate, shift) and
+    aug_rotate: Optional[float] = None               # color (brightness, contrast, gamma); None = AugmentSpec's
+    aug_shift: Optional[float] = None                # default
+    aug_brightness: Optional[float] = None
+    aug_contrast: Optional[float] = None
+    aug_gamma: Optional[float] = None
     out_dir: str = "."
     device: Optional[str] = None
     stages: int = 2                                  # pipeline stages for -t MP
@@ -72,6 +79,15 @@ class TrainConfig:
         return asdict(self)
 
 
+def _augment_spec(text: str) -> str:
+    """``--augment``: the canonical spec string (``color+hflip`` -> ``hflip+color``)."""
+    from .data.augment import canonical
+    try:
+        return canonical(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Train UNet on images and target masks (MI355X-native)")
     p.add_argument("--train-method", "-t", type=str, default="singleGPU", help="singleGPU | DP | DDP | MP")
@@ -102,9 +118,21 @@ def build_parser() -> argparse.ArgumentParser:
                         "and keep the set in HBM as uint8; batches are gathered on the device (on a CPU "
                         "device the same dataset holds PIL's results). --num-workers = decode threads "
                         "(0: min(8, cores))")
-    p.add_argument("--augment", choices=["none", "hflip"], default="none",
-                   help="training augmentation of the resident folder data (needs --device-folder-data): hflip = "
-                        "mirror image and mask where a hash of (seed, epoch, item) is odd")
+    p.add_argument("--augment", type=_augment_spec, default="none", metavar="SPEC",
+                   help="training augmentation of the resident folder data (needs --device-folder-data): none, or "
+                        "names joined by + from hflip (mirror image and mask where a hash of (seed, epoch, item) "
+                        "is odd), affine (random zoom, rotation and shift of image and mask together) and color "
+                        "(brightness, contrast and gamma of the image); all drawn from hashes of (seed, epoch, "
+                        "item) and applied in the batch kernel")
+    for name, family, what in (
+            ("scale", "affine", "zoom log-uniform in [1/(1+S), 1+S] (default 0.25)"),
+            ("rotate", "affine", "degrees, uniform in +-R (default 10)"),
+            ("shift", "affine", "fraction of W and of H, uniform in +-F (default 0.10)"),
+            ("brightness", "color", "additive in the unit range, uniform in +-B (default 0.2)"),
+            ("contrast", "color", "factor about 0.5, uniform in [1-C, 1+C] (default 0.2)"),
+            ("gamma", "color", "exponent log-uniform in [1/(1+G), 1+G] (default 0.2)")):
+        p.add_argument(f"--aug-{name}", type=float, default=None,
+                       help=f"--augment ...{family}...: {what}")
     p.add_argument("--out-dir", type=str, default=".")
     p.add_argument("--device", type=str, default=None)
     p.add_argument("--stages", type=int, default=2)
@@ -155,6 +183,18 @@ def parse_args(argv=None) -> TrainConfig:
     if a.augment != "none" and not a.device_folder_data:
         raise SystemExit(f"--augment {a.augment} needs --device-folder-data: the augmentation runs in the "
                          "resident folder dataset's batch kernel, the host DataLoader path has none")
+    from .data.augment import AFFINE_MAGNITUDES, MAGNITUDES
+    for m in MAGNITUDES:
+        v = getattr(a, f"aug_{m}")
+        if v is None:
+            continue
+        family = "affine" if m in AFFINE_MAGNITUDES else "color"
+        if family not in a.augment.split("+"):
+            raise SystemExit(f"--aug-{m} has no effect with --augment {a.augment}: add {family} to --augment")
+        if v < 0.0:
+            raise SystemExit(f"--aug-{m} {v}: a magnitude cannot be negative")
+        if not 0.0 <= v < float("inf"):                      # nan, inf
+            raise SystemExit(f"--aug-{m} {v}: a magnitude must be finite")
     size = a.img_size
     img_size = (size[0], size[0]) if len(size) == 1 else (size[0], size[1])
     cfg = TrainConfig(
@@ -162,7 +202,9 @@ def parse_args(argv=None) -> TrainConfig:
         batch_size=a.batch_size, checkpoint=a.checkpoint, seed=a.seed, img_size=img_size,
         dtype=a.dtype, backend=a.backend, model=a.model, synthetic=a.synthetic,
         synthetic_len=a.synthetic_len, device_data=a.device_data, data_dir=a.data_dir,
-        device_folder_data=a.device_folder_data, augment=a.augment, out_dir=a.out_dir, device=a.device,
+        device_folder_data=a.device_folder_data, augment=a.augment, aug_scale=a.aug_scale,
+        aug_rotate=a.aug_rotate, aug_shift=a.aug_shift, aug_brightness=a.aug_brightness, aug_contrast=a.aug_contrast,
+        aug_gamma=a.aug_gamma, out_dir=a.out_dir, device=a.device,
         stages=a.stages, microbatches=a.microbatches, mp_cut=a.mp_cut, mp_replicas=a.mp_replicas, bucket_mb=a.bucket_mb,
         grad_comm_dtype=a.grad_comm_dtype,
         comm_overlap=a.comm_overlap, global_dice=a.global_dice,

@@ -19,6 +19,13 @@ GPU has 288 GB, so (opt-in, ``--device-folder-data``):
 * ``augment="hflip"`` (training loader): item ``i`` of epoch ``e`` is mirrored, image and mask together, when
   :func:`flip_flags` -- a fixed integer hash of ``(seed, e, base index i)`` -- is odd: a pure function, so a
   resumed run replays it and every pipeline stage agrees.
+* ``augment`` with ``affine`` or ``color`` (:class:`.augment.AugmentSpec`: names from ``hflip``, ``affine``,
+  ``color`` joined by ``+``, canonically in that order): the batch is ONE launch of ``dpa_batch_augment_u8``
+  (csrc/augment.hip) instead -- per item an inverse affine map (random zoom, rotation, shift and the mirror;
+  bilinear for the image, nearest for the mask, clamp-to-edge) and a 256-entry tone table (brightness, contrast,
+  gamma), both built on the host per batch from hashes of ``(seed, e, i, stream)`` and uploaded (B x 6 int32 and
+  B x 256 float32).  Integer arithmetic, specified in ``augment.py``: the kernel, the CPU path
+  (``augment_reference``) and the tests agree bit for bit.
 
 With DDP or ``-t MP`` every rank loads the FULL resized set: the shards change per epoch and the stages of a
 pipeline pair their batches by order.  Sharding the load is out of scope here.
@@ -35,11 +42,11 @@ import numpy as np
 import torch
 from torch.utils.data import BatchSampler, Subset
 
+from .augment import AugmentSpec, affine_matrices, augment_reference, color_luts
 from .folder import BasicDataset, _load_image
 
 log = logging.getLogger(__name__)
 
-AUGMENTS = ("none", "hflip")
 _IMAGE_MODES = ("L", "RGB")       # what dpa_resize_bicubic_u8 covers: 8-bit, 1 or 3 interleaved channels
 _MASK_MODES = ("L", "P")          # single-channel 8-bit: grey levels or palette indices (GIF)
 
@@ -183,11 +190,15 @@ class DeviceFolderLoader:
     """Batches assembled on the device; yields ``(images, targets)`` like ``loaders.DeviceBatcher``.
 
     ``augment="hflip"`` mirrors the items :func:`flip_flags` selects for the sampler's current epoch
-    (``set_epoch``); ``last_flags`` holds the flags of the batch yielded last (None without augmentation)."""
+    (``set_epoch``); ``last_flags`` holds the flags of the batch yielded last (None without ``hflip``).
+    ``augment`` is a spec string or an :class:`.augment.AugmentSpec` (which carries the magnitudes); with
+    ``affine`` or ``color`` in it every batch is warped and toned by ``dpa_batch_augment_u8``, and ``last_params``
+    holds the host ``(mats int32 [B,6], luts float32 [B,256] or None)`` of the batch yielded last."""
 
-    def __init__(self, dataset, batch_size: int, sampler=None, drop_last: bool = False, augment: str = "none",
+    def __init__(self, dataset, batch_size: int, sampler=None, drop_last: bool = False, augment="none",
                  seed: int = 0):
-        assert augment in AUGMENTS, f"unknown augment {augment!r}; choose from {AUGMENTS}"
+        self.spec = AugmentSpec.parse(augment)                  # ValueError names the valid ones
+        augment = self.spec.name
         self.base, idx = _base(dataset)
         self.n = len(dataset)
         self.index_map = idx                                   # host: the flip hash is on base indices
@@ -195,6 +206,7 @@ class DeviceFolderLoader:
         self.batches = BatchSampler(self.sampler, batch_size, drop_last)
         self.augment, self.seed = augment, int(seed)
         self.last_flags: Optional[np.ndarray] = None
+        self.last_params = None
 
     def __len__(self):
         return len(self.batches)
@@ -207,8 +219,21 @@ class DeviceFolderLoader:
             if self.index_map is not None:
                 i = self.index_map.index_select(0, i)
             assert int(i.min()) >= 0 and int(i.max()) < len(base), "sampler index outside the dataset"
-            flags = flip_flags(self.seed, epoch, i.numpy()) if self.augment == "hflip" else None
+            flags = flip_flags(self.seed, epoch, i.numpy()) if self.spec.hflip else None
             self.last_flags = flags
+            if self.spec.warps:
+                luts = color_luts(self.spec, self.seed, epoch, i.numpy())
+                mats = torch.from_numpy(affine_matrices(self.spec, self.seed, epoch, i.numpy(), base.h, base.w))
+                luts = None if luts is None else torch.from_numpy(luts)
+                self.last_params = (mats, luts)
+                if base.on_gpu:
+                    from ..ops import kernels as K
+                    yield K.batch_augment_u8(base.images, base.masks, i.to(dev, non_blocking=True),
+                                             mats.to(dev, non_blocking=True),
+                                             None if luts is None else luts.to(dev, non_blocking=True))
+                else:
+                    yield augment_reference(base.images, base.masks, i, mats, luts)
+                continue
             if base.on_gpu:
                 from ..ops import kernels as K
                 f = None if flags is None else torch.from_numpy(flags).to(dev, non_blocking=True)
@@ -224,9 +249,9 @@ class DeviceFolderLoader:
 
 
 def device_folder_loaders(train_set, val_set, batch_size: int, *, rank: int = 0, world_size: int = 1, seed: int = 0,
-                          drop_last: bool = False, augment: str = "none"):
-    """``loaders.build_loaders`` for a resident folder dataset (same samplers, same batches); ``augment``
-    applies to the training loader only."""
+                          drop_last: bool = False, augment="none"):
+    """``loaders.build_loaders`` for a resident folder dataset (same samplers, same batches); ``augment`` (a
+    spec string or an ``AugmentSpec``) applies to the training loader only."""
     from torch.utils.data.distributed import DistributedSampler
     from .loaders import EpochShuffleSampler
     val_sampler: Optional[object] = None

@@ -1703,6 +1703,40 @@ def batch_gather_u8(images: torch.Tensor, masks: torch.Tensor, idx: torch.Tensor
     return img, tgt
 
 
+def batch_augment_u8(images: torch.Tensor, masks: torch.Tensor, idx: torch.Tensor, mats: torch.Tensor,
+                     luts: Optional[torch.Tensor] = None, out=None):
+    """``batch_gather_u8`` with a warp and a tone curve per item (csrc/augment.hip; the arithmetic is
+    ``data.augment.augment_reference``'s, bit for bit): ``mats`` int32 ``[B, 6]`` is the inverse affine map of each
+    item in Q16 (output pixel index -> source pixel index; bilinear for the image, nearest for the mask,
+    clamp-to-edge), ``luts`` float32 ``[B, 256]`` the table each item's interpolated byte goes through
+    (None: ``unit_table`` for all).  ``out``: ``(img, tgt)`` to write into instead of new tensors."""
+    _u8(images, "batch_augment.images")
+    _u8(masks, "batch_augment.masks")
+    assert images.dim() == 4 and masks.dim() == 3 and images.device == masks.device
+    N, C, H, W = images.shape
+    assert tuple(masks.shape) == (N, H, W), f"batch_augment: masks {tuple(masks.shape)} for images {tuple(images.shape)}"
+    assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and idx.device == images.device
+    B = idx.numel()
+    assert B > 0 and N > 0
+    assert mats.dtype == torch.int32 and tuple(mats.shape) == (B, 6) and mats.is_contiguous() \
+        and mats.device == images.device, f"batch_augment: mats {mats.dtype} {tuple(mats.shape)} on {mats.device}"
+    if luts is not None:
+        assert luts.dtype == torch.float32 and tuple(luts.shape) == (B, 256) and luts.is_contiguous() \
+            and luts.device == images.device, f"batch_augment: luts {luts.dtype} {tuple(luts.shape)} on {luts.device}"
+    if out is None:
+        img = torch.empty(B, C, H, W, dtype=torch.float32, device=images.device)
+        tgt = torch.empty(B, 1, H, W, dtype=torch.float32, device=images.device)
+    else:
+        img, tgt = out
+        for t, shape in ((img, (B, C, H, W)), (tgt, (B, 1, H, W))):
+            assert t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous() \
+                and t.device == images.device, f"batch_augment: out {t.dtype} {tuple(t.shape)} on {t.device}"
+    _check(_lib.lib().dpa_batch_augment_u8(_p(images), _p(masks), _p(idx), _p(mats), _p(luts),
+                                           _p(unit_table(images.device)), _p(img), _p(tgt), c_ll(N), c_int(B),
+                                           c_int(C), c_int(H), c_int(W), _stream(images)), "batch_augment_u8")
+    return img, tgt
+
+
 # ------------------------------------------------------------------------------ prediction post-processing (csrc/predict_post.hip)
 PREDICT_KMAX = 9             # taps per axis dpa_prob_to_mask_u8 accepts (down-scaling up to 4x)
 

@@ -542,9 +542,13 @@ def train(cfg: TrainConfig):
             train_set, val_set, cfg.batch_size, rank=dp_rank, world_size=dp_ranks, seed=cfg.seed,
             drop_last=strat.name in ("MP",))
     elif isinstance(_base_dataset(train_set), DeviceFolderDataset):
+        from .data.augment import spec_from_config
+        spec = spec_from_config(cfg)
+        if spec.name != "none":
+            log.info(f"augment: {spec.describe()} (hashes of seed {cfg.seed}, epoch and item; training batches only)")
         train_loader, val_loader, sampler = device_folder_loaders(
             train_set, val_set, cfg.batch_size, rank=dp_rank, world_size=dp_ranks, seed=cfg.seed,
-            drop_last=strat.name in ("MP",), augment=cfg.augment)
+            drop_last=strat.name in ("MP",), augment=spec)
     else:
         train_loader, val_loader, sampler = build_loaders(
             train_set, val_set, cfg.batch_size, rank=dp_rank, world_size=dp_ranks, num_workers=cfg.num_workers,
