@@ -10,9 +10,14 @@
 //                        source rows its current output row reads in a register window and computes a source row
 //                        once, when the window reaches it (2x up-scaling: one new source row per two output rows).
 //                        The build contracts a * b + c into an fma and PIL's double sums are a rounded multiply,
-//                        then a rounded add: contraction is switched off in the kernel.  An axis whose sizes are
+//                        then a rounded add: contraction is switched off in the walk (by a pragma, which the build honours
+//                        for this file: tools/build_hip.py FILE_FLAGS).  An axis whose sizes are
 //                        equal carries the identity table (one coefficient 1.0: 0.0 + p * 1.0 == p), so "pass
 //                        skipped" needs no second kernel.
+//   dpa_prob_score       the same resize, compared with up to 8 thresholds and with ground-truth bytes [B][H][W]
+//                        (a pixel is truth where its byte > cut[b]) and counted instead of stored: int64
+//                        [B][1 + 2T] = (truth, pred_0, inter_0, ...), what the Dice coefficient and the IoU of the
+//                        full-size masks at every threshold are made of, without a mask being written.
 //   dpa_mask_rle         uint8 masks [B][H][W] -> the maximal runs of non-zero bytes of each flattened image as
 //                        (start, length), start 1-indexed, ascending; counts[b] is the true number of runs, nothing
 //                        is written past cap.  With a zero in front of the first pixel and behind the last, the
@@ -37,22 +42,15 @@ static __device__ __forceinline__ int pp_clamp(int v, int lo, int hi) { return v
 // Workgroup: 64 output columns x 4 chunks of PP_ROWS output rows (one wave per chunk), grid.z = image.
 // KM: the taps per axis this instantiation holds in registers (3: up-scaling and identity; 9: down-scaling).
 // Everything that depends on the output row alone is uniform in a wave; only the column differs between lanes.
-template <int KM>
-__global__ __launch_bounds__(PP_THREADS) void prob_to_mask_u8_kernel(
-    const float* __restrict__ probs, int h, int w, unsigned char* __restrict__ dst, int H, int W,
-    const int* __restrict__ hb, const double* __restrict__ hc, int kh, const int* __restrict__ vb,
-    const double* __restrict__ vc, int kv, float threshold, unsigned value) {
+//
+// pp_walk is the resize itself, shared by the mask kernel and the scoring kernel: output column xc (< W) of image
+// `img`, output rows ya .. yb - 1, emit(y, value) per row with value the float32 PIL stores.
+template <int KM, class Emit>
+static __device__ __forceinline__ void pp_walk(const float* __restrict__ img, int h, int w, int xc, int ya, int yb,
+                                               const int* __restrict__ hb, const double* __restrict__ hc, int kh,
+                                               const int* __restrict__ vb, const double* __restrict__ vc, int kv,
+                                               Emit emit) {
 #pragma clang fp contract(off)
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ya = (blockIdx.y * 4 + chunk) * PP_ROWS;
-  if (ya >= H) return;                           // the whole wave; there is no barrier in this kernel
-  const int yb = min(ya + PP_ROWS, H);
-  const bool live = x < W;
-  const int xc = live ? x : W - 1;               // lanes right of the image compute its last column, store nothing
-  const float* img = probs + (long)blockIdx.z * h * w;
-  unsigned char* out = dst + (long)blockIdx.z * H * W;
-
   // this column's horizontal taps
   const int xm = pp_clamp(hb[2 * xc], 0, w);
   const int nh = pp_clamp(hb[2 * xc + 1], 0, min(min(kh, KM), w - xm));
@@ -97,7 +95,118 @@ __global__ __launch_bounds__(PP_THREADS) void prob_to_mask_u8_kernel(
         const double m = (double)win[r] * ky[r];
         sv = sv + m;
       }
-    if (live) out[(long)y * W + x] = (unsigned char)((float)sv > threshold ? value : 0u);
+    emit(y, (float)sv);
+  }
+}
+
+template <int KM>
+__global__ __launch_bounds__(PP_THREADS) void prob_to_mask_u8_kernel(
+    const float* __restrict__ probs, int h, int w, unsigned char* __restrict__ dst, int H, int W,
+    const int* __restrict__ hb, const double* __restrict__ hc, int kh, const int* __restrict__ vb,
+    const double* __restrict__ vc, int kv, float threshold, unsigned value) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ya = (blockIdx.y * 4 + chunk) * PP_ROWS;
+  if (ya >= H) return;                           // the whole wave; there is no barrier in this kernel
+  const int yb = min(ya + PP_ROWS, H);
+  const bool live = x < W;
+  const int xc = live ? x : W - 1;               // lanes right of the image compute its last column, store nothing
+  unsigned char* out = dst + (long)blockIdx.z * H * W;
+  pp_walk<KM>(probs + (long)blockIdx.z * h * w, h, w, xc, ya, yb, hb, hc, kh, vb, vc, kv, [&](int y, float v) {
+    if (live) out[(long)y * W + x] = (unsigned char)(v > threshold ? value : 0u);
+  });
+}
+
+// ------------------------------------------------------------------------------ resize + threshold + count
+// The mask kernel's grid and walk, but nothing is stored per pixel: a lane compares its 16 values with up to 8
+// thresholds and with the ground truth (byte > cut[image]) and counts.  A workgroup covers at most 64 x 64 = 4096
+// pixels, so a pair (pred_t, inter_t) is counted in the two halves of one 32-bit register: + 1 for "predicted",
+// + 0x10000 more where the pixel is truth as well.  Lanes right of the image and rows below it add nothing.  The
+// wave sums by shuffles, the four waves through LDS, and the workgroup writes row (blockIdx.y * gridDim.x +
+// blockIdx.x) of work [B][blocks][1 + 2T] = (truth, pred_0, inter_0, ...) with plain stores; score_sum_kernel adds
+// an image's rows up.  No atomics, nothing to zero.
+struct PPThresholds { float v[8]; };             // by value in the kernel arguments: no device table, no copy
+
+static __device__ __forceinline__ unsigned pp_wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;                                      // lane 0 holds the sum
+}
+
+// NT: the thresholds this instantiation counts (1 or 8); thr.v[t] for T <= t < NT is +infinity and counts nothing.
+template <int KM, int NT>
+__global__ __launch_bounds__(PP_THREADS) void prob_score_kernel(
+    const float* __restrict__ probs, int h, int w, const unsigned char* __restrict__ truth,
+    const int* __restrict__ cut, int H, int W, const int* __restrict__ hb, const double* __restrict__ hc, int kh,
+    const int* __restrict__ vb, const double* __restrict__ vc, int kv, PPThresholds thr, int T,
+    unsigned* __restrict__ work) {
+  __shared__ unsigned red[4][NT + 1];
+  const int lane = threadIdx.x & 63;
+  const int x = blockIdx.x * 64 + lane;
+  const int chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ya = min((int)(blockIdx.y * 4 + chunk) * PP_ROWS, H);   // a wave below the image walks no row and still
+  const int yb = min(ya + PP_ROWS, H);                         // reaches the barrier
+  const bool live = x < W;
+  const int xc = live ? x : W - 1;
+  const unsigned char* tr = truth + (long)blockIdx.z * H * W;
+  const int cutv = cut[blockIdx.z];
+
+  // bit r: the pixel of row ya + r is truth.  Loaded up front, so the bytes arrive while the walk computes.
+  unsigned tbits = 0;
+#pragma unroll
+  for (int r = 0; r < PP_ROWS; ++r)
+    if (live && ya + r < yb) tbits |= ((int)tr[(long)(ya + r) * W + x] > cutv ? 1u : 0u) << r;
+
+  unsigned acc[NT];                              // low half: pred_t, high half: inter_t
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = 0u;
+  pp_walk<KM>(probs + (long)blockIdx.z * h * w, h, w, xc, ya, yb, hb, hc, kh, vb, vc, kv, [&](int y, float v) {
+    const unsigned inc = live ? 1u + (((tbits >> (y - ya)) & 1u) << 16) : 0u;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] += v > thr.v[t] ? inc : 0u;
+  });
+
+  const unsigned nt = pp_wave_sum((unsigned)__popc(tbits));
+  if (lane == 0) red[chunk][0] = nt;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const unsigned s = pp_wave_sum(acc[t]);      // at most 1024 in either half
+    if (lane == 0) red[chunk][1 + t] = s;
+  }
+  __syncthreads();
+  const int n = 1 + 2 * T, k = threadIdx.x;
+  if (k < n) {
+    const int c = (k + 1) >> 1;                  // red column: 0 truth; 1 + t for pred_t (odd k) and inter_t (even k)
+    const unsigned s = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+    const long row = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    work[row * n + k] = k == 0 ? s : ((k & 1) ? (s & 0xffffu) : (s >> 16));
+  }
+}
+
+// one workgroup per image: counts [B][n] = the sums over the image's `blocks` rows of work, in int64
+__global__ __launch_bounds__(PP_THREADS) void score_sum_kernel(const unsigned* __restrict__ work, int blocks, int n,
+                                                               long long* __restrict__ counts) {
+  __shared__ long long red[4][17];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned* wk = work + (long)blockIdx.x * blocks * n;
+  long long acc[17];
+#pragma unroll
+  for (int k = 0; k < 17; ++k) acc[k] = 0;
+  for (int r = threadIdx.x; r < blocks; r += PP_THREADS)
+#pragma unroll
+    for (int k = 0; k < 17; ++k)
+      if (k < n) acc[k] += (long long)wk[(long)r * n + k];
+#pragma unroll
+  for (int k = 0; k < 17; ++k) {
+    long long v = acc[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) red[wv][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < n) {
+    const int k = threadIdx.x;
+    counts[(long)blockIdx.x * n + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
   }
 }
 
@@ -126,6 +235,50 @@ DPA_API int dpa_prob_to_mask_u8(const float* probs, int B, int h, int w, unsigne
   else
     hipLaunchKernelGGL((prob_to_mask_u8_kernel<PP_KMAX>), grid, dim3(PP_THREADS), 0, st, probs, h, w, dst, H, W, hb, hc,
                        kh, vb, vc, kv, threshold, (unsigned)value);
+  return (int)hipGetLastError();
+}
+
+// workgroups (= rows of `work`) per image of dpa_prob_score; 0 for sizes the launcher rejects
+DPA_API int dpa_prob_score_blocks(int H, int W) {
+  if (H < 1 || W < 1 || (long)H * W >= (1l << 31)) return 0;
+  const long gx = ((long)W + 63) / 64, gy = ((long)H + 4 * PP_ROWS - 1) / (4 * PP_ROWS);
+  return gy > 65535 ? 0 : (int)(gx * gy);        // H * W < 2^31: gx * gy < 2^20 + gx + gy
+}
+
+// counts int64 [B][1 + 2T] = (truth, pred_0, inter_0, ...): truth pixels (byte > cut[b]), pixels whose resized
+// probability is > thresholds[t], and those that are both.  `thresholds` is a HOST array: it travels in the
+// kernel arguments, so the two launches can be captured in a graph.
+DPA_API int dpa_prob_score(const float* probs, int B, int h, int w, const unsigned char* truth, const int* cut, int H,
+                           int W, const int* hb, const double* hc, int kh, const int* vb, const double* vc, int kv,
+                           const float* thresholds, int T, long long* counts, unsigned* work, long long work_elems,
+                           hipStream_t st) {
+  if (B < 1 || h < 1 || w < 1 || H < 1 || W < 1 || T < 1 || T > 8) return (int)hipErrorInvalidValue;
+  if (!probs || !truth || !cut || !hb || !hc || !vb || !vc || !thresholds || !counts || !work)
+    return (int)hipErrorInvalidValue;
+  if ((long)h * w >= (1l << 31) || (long)H * W >= (1l << 31)) return (int)hipErrorInvalidValue;
+  if (kh != pp_ksize(w, W) || kv != pp_ksize(h, H)) return (int)hipErrorInvalidValue;
+  if (kh > PP_KMAX || kv > PP_KMAX) return (int)hipErrorInvalidValue;       // the caller scores on the host
+  const int blocks = dpa_prob_score_blocks(H, W);
+  if (blocks < 1 || B > 65535) return (int)hipErrorInvalidValue;
+  const int n = 1 + 2 * T;
+  if (work_elems < (long long)B * blocks * n) return (int)hipErrorInvalidValue;
+  PPThresholds thr;
+  for (int t = 0; t < 8; ++t) thr.v[t] = t < T ? thresholds[t] : INFINITY;
+  const unsigned gx = (unsigned)(((long)W + 63) / 64);
+  const dim3 grid(gx, (unsigned)blocks / gx, (unsigned)B);
+#define PP_SCORE(KM, NT)                                                                                              \
+  hipLaunchKernelGGL((prob_score_kernel<KM, NT>), grid, dim3(PP_THREADS), 0, st, probs, h, w, truth, cut, H, W, hb,  \
+                     hc, kh, vb, vc, kv, thr, T, work)
+  const bool small = kh <= 3 && kv <= 3;
+  if (T == 1) {
+    if (small) PP_SCORE(3, 1); else PP_SCORE(PP_KMAX, 1);
+  } else {
+    if (small) PP_SCORE(3, 8); else PP_SCORE(PP_KMAX, 8);
+  }
+#undef PP_SCORE
+  const int err = (int)hipGetLastError();
+  if (err) return err;
+  hipLaunchKernelGGL(score_sum_kernel, dim3(B), dim3(PP_THREADS), 0, st, (const unsigned*)work, blocks, n, counts);
   return (int)hipGetLastError();
 }
 

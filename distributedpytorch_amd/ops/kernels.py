@@ -1867,3 +1867,75 @@ def mask_rle(masks: torch.Tensor, cap: int):
     _check(L.dpa_mask_rle(_p(masks), c_int(B), c_int(H), c_int(W), _p(runs), c_int(int(cap)), _p(counts), _p(work),
                           c_ll(work.numel()), _stream(masks)), "mask_rle")
     return runs, counts
+
+
+SCORE_TMAX = 8               # thresholds one dpa_prob_score launch counts
+
+
+def score_reference(prob, truth_u8, cut: int, thresholds):
+    """The definition of the scoring counts, in numpy + PIL: float32 probabilities ``[h, w]`` resized by PIL (mode
+    ``F``, BILINEAR) to the truth's size ``[H, W]``; a pixel is predicted at threshold ``t`` where the resized value
+    is ``> float32(t)`` and is truth where ``truth_u8 > cut``.  Returns int64 ``[1 + 2T]`` = (truth, pred_0,
+    inter_0, ..., pred_{T-1}, inter_{T-1}) with ``inter_t`` the pixels that are both."""
+    import numpy as np
+    from PIL import Image
+    truth = np.asarray(truth_u8) > cut
+    H, W = truth.shape
+    p = np.ascontiguousarray(prob, dtype=np.float32)
+    r = np.asarray(Image.fromarray(p).resize((W, H), resample=Image.BILINEAR))      # float32 -> mode F
+    out = [int(truth.sum())]
+    for t in thresholds:
+        pred = r > np.float32(t)
+        out += [int(pred.sum()), int((pred & truth).sum())]
+    return np.array(out, np.int64)
+
+
+def dice_iou(counts):
+    """Counts ``[..., 1 + 2T]`` as ``prob_score`` / ``score_reference`` give them -> (``dice [..., T]``,
+    ``iou [..., T]``) in float64: ``2 inter / (pred + truth)`` and ``inter / (pred + truth - inter)``; both are 1.0
+    where prediction and truth are both empty (the Carvana convention)."""
+    import numpy as np
+    c = np.asarray(counts.cpu() if isinstance(counts, torch.Tensor) else counts).astype(np.float64)
+    assert c.shape[-1] >= 3 and c.shape[-1] % 2 == 1, f"dice_iou: last axis must be 1 + 2T, got {c.shape}"
+    truth, pred, inter = c[..., :1], c[..., 1::2], c[..., 2::2]
+    total = pred + truth
+    empty = total == 0
+    safe = np.where(empty, 1.0, total)
+    dice = np.where(empty, 1.0, 2.0 * inter / safe)
+    iou = np.where(empty, 1.0, inter / np.where(empty, 1.0, total - inter))
+    return dice, iou
+
+
+def prob_score(probs: torch.Tensor, truth: torch.Tensor, cut: torch.Tensor, thresholds):
+    """``probs`` float32 ``[B, h, w]``, ``truth`` uint8 ``[B, H, W]``, ``cut`` int32 ``[B]`` (all on one GPU) and
+    1 to 8 ``thresholds`` (host floats, any order) -> int64 ``[B, 1 + 2T]`` on the device, per image what
+    ``score_reference`` returns.  One launch resizes (PIL's mode-``F`` bilinear, bit-equal), compares and counts
+    in registers; no mask is written.  Returns None, without launching, when an axis is down-scaled by more
+    than 4x: the caller then scores on the host."""
+    _u8(truth, "prob_score.truth")
+    assert probs.dtype == torch.float32 and probs.is_cuda and probs.is_contiguous(), \
+        f"prob_score.probs: need a contiguous cuda float32 tensor, got {probs.dtype} {tuple(probs.shape)} on {probs.device}"
+    assert cut.dtype == torch.int32 and cut.is_contiguous() and cut.device == probs.device, \
+        f"prob_score.cut: need a contiguous int32 tensor on {probs.device}, got {cut.dtype} on {cut.device}"
+    assert probs.dim() == 3 and truth.dim() == 3 and probs.device == truth.device
+    assert probs.shape[0] == truth.shape[0] == cut.numel() and cut.dim() == 1
+    thr = [float(t) for t in thresholds]
+    T = len(thr)
+    assert 1 <= T <= SCORE_TMAX, f"prob_score: 1 to {SCORE_TMAX} thresholds, got {T}"
+    B, h, w = probs.shape
+    _, H, W = truth.shape
+    assert min(B, h, w, H, W) > 0
+    hb, hc, kh = _bilinear_device_table(w, W, probs.device)
+    vb, vc, kv = _bilinear_device_table(h, H, probs.device)
+    if kh > PREDICT_KMAX or kv > PREDICT_KMAX:
+        return None
+    L = _lib.lib()
+    blocks = int(L.dpa_prob_score_blocks(c_int(H), c_int(W)))
+    assert blocks > 0, f"prob_score: {H}x{W} is beyond the launcher's limits"
+    counts = torch.empty(B, 1 + 2 * T, dtype=torch.int64, device=probs.device)
+    work = torch.empty(B * blocks * (1 + 2 * T), dtype=torch.int32, device=probs.device)
+    host_thr = (ctypes.c_float * T)(*thr)            # read by the launcher before it returns
+    _check(L.dpa_prob_score(_p(probs), c_int(B), c_int(h), c_int(w), _p(truth), _p(cut), c_int(H), c_int(W),
+                            _p(hb), _p(hc), c_int(kh), _p(vb), _p(vc), c_int(kv), host_thr, c_int(T), _p(counts),
+                            _p(work), c_ll(work.numel()), _stream(probs)), "prob_score")
+    return counts

@@ -19,6 +19,13 @@ The host path -- PIL ``resize(BILINEAR)`` of the float32 probabilities, ``> thre
 defines the result.  It serves a CPU device, ``host_post=True`` (A/B comparison, debugging), a source size the
 resize kernel refuses (down-scaling beyond 4x) and a run list that overflows its capacity; ``host_finished``
 counts the files it finished.  Nothing is timed or synchronised per image: the downloads are per batch.
+
+:meth:`Predictor.score_files` compares those full-size masks with mask files, which is how the dataset is scored:
+the mean over the images of the Dice coefficient at the source resolution.  The decode threads load the mask next
+to the image; per group of equal source sizes one ``dpa_prob_score`` launch resizes, thresholds (up to 8
+thresholds at once) and counts truth, predicted and common pixels in registers, so no mask exists on the device
+and a few integers per image come back.  ``ops.kernels.score_reference`` (PIL + numpy) defines the counts and is
+the host path.
 """
 from __future__ import annotations
 
@@ -192,29 +199,137 @@ class Predictor:
                 out[i] = self._host_finish(sel[j], sizes[i], want_masks, want_rle)
         return [tuple(o) for o in out]
 
+    def score(self, probs: torch.Tensor, truths: Sequence, cuts: Sequence, thresholds: Sequence,
+              count_host: bool = True) -> np.ndarray:
+        """``probs`` float32 ``[B, h, w]`` against per image a truth array uint8 ``[Hs, Ws]`` (a pixel is truth
+        where its byte ``> cuts[i]``) -> int64 ``[B, 1 + 2T]`` = (truth, pred_0, inter_0, ...) as
+        ``ops.kernels.score_reference`` defines them.  On a GPU one ``dpa_prob_score`` launch per group of equal
+        source sizes and one download of the counts; no mask is materialised.  ``count_host=False``: the files
+        finished on the host are not added to ``host_finished`` (``post`` counted them already)."""
+        from .ops import kernels as K
+        B, T = probs.shape[0], len(thresholds)
+        assert len(truths) == len(cuts) == B and 1 <= T <= K.SCORE_TMAX
+        out = np.empty((B, 1 + 2 * T), np.int64)
+        todo, launched = list(range(B)), []
+        if not self.host_post:
+            groups = {}
+            for i, t in enumerate(truths):
+                groups.setdefault(tuple(t.shape), []).append(i)
+            todo = []
+            for idx in groups.values():
+                sel = probs if len(idx) == B else probs.index_select(0, torch.tensor(idx, device=probs.device))
+                truth = torch.from_numpy(np.stack([truths[i] for i in idx])).to(probs.device, non_blocking=True)
+                cut = torch.tensor([int(cuts[i]) for i in idx], dtype=torch.int32).to(probs.device, non_blocking=True)
+                counts = K.prob_score(sel, truth, cut, thresholds)
+                if counts is None:
+                    todo += idx
+                else:
+                    launched.append((idx, counts))
+            if launched:
+                out[[i for idx, _ in launched for i in idx]] = torch.cat([c for _, c in launched]).cpu().numpy()
+        if todo:
+            todo = sorted(todo)
+            host = (probs if len(todo) == B else
+                    probs.index_select(0, torch.tensor(todo, device=probs.device))).cpu().numpy()
+            for j, i in enumerate(todo):
+                out[i] = K.score_reference(host[j], truths[i], int(cuts[i]), thresholds)
+            if count_host:
+                self.host_finished += len(todo)
+        return out
+
     # ---- files --------------------------------------------------------------------------------------------
-    def predict_files(self, paths, batch_size: int = 4, workers: int = 0, want_masks: bool = True,
-                      want_rle: bool = True) -> Iterator:
-        """Yields ``(path, (Hs, Ws), mask uint8 [Hs, Ws] or None, runs int32 [n, 2] or None)`` per file, in input
-        order.  ``workers``: decode threads; 0 means ``min(8, os.cpu_count())``; never more than 16."""
-        paths = list(paths)
+    def _decode_pair(self, pair):
+        """``_decode`` of the image plus the truth of the mask file next to it: uint8 ``[Hs, Ws]`` and ``cut``."""
+        size, arr, raw = self._decode(pair[0])
+        truth, cut = load_truth(pair[1], size, pair[0])
+        return size, arr, raw, truth, cut
+
+    def _batches(self, jobs, decode, batch_size: int, workers: int) -> Iterator:
+        """``(jobs of one batch, their decoded items)`` in input order, decoded by a bounded thread pool."""
+        jobs = list(jobs)
         batch_size = max(1, int(batch_size))
         workers = max(1, min(16, int(workers) if workers else min(8, os.cpu_count() or 1)))
         pending = deque()
         with ThreadPoolExecutor(workers) as pool:
             nxt = 0
-            for b0 in range(0, len(paths), batch_size):
-                chunk = paths[b0:b0 + batch_size]
+            for b0 in range(0, len(jobs), batch_size):
+                chunk = jobs[b0:b0 + batch_size]
                 items = []
                 for _ in chunk:
-                    while nxt < len(paths) and len(pending) < max(2 * workers, batch_size):   # bounded: full-size sources
-                        pending.append(pool.submit(self._decode, paths[nxt]))
+                    while nxt < len(jobs) and len(pending) < max(2 * workers, batch_size):   # bounded: full-size sources
+                        pending.append(pool.submit(decode, jobs[nxt]))
                         nxt += 1
                     items.append(pending.popleft().result())
-                sizes = [s for s, _, _ in items]
-                res = self.post(self.probs(self._inputs(items)), sizes, want_masks, want_rle)
-                for p, s, (m, r) in zip(chunk, sizes, res):
-                    yield p, s, m, r
+                yield chunk, items
+
+    def predict_files(self, paths, batch_size: int = 4, workers: int = 0, want_masks: bool = True,
+                      want_rle: bool = True) -> Iterator:
+        """Yields ``(path, (Hs, Ws), mask uint8 [Hs, Ws] or None, runs int32 [n, 2] or None)`` per file, in input
+        order.  ``workers``: decode threads; 0 means ``min(8, os.cpu_count())``; never more than 16."""
+        for chunk, items in self._batches(paths, self._decode, batch_size, workers):
+            sizes = [s for s, _, _ in items]
+            res = self.post(self.probs(self._inputs(items)), sizes, want_masks, want_rle)
+            for p, s, (m, r) in zip(chunk, sizes, res):
+                yield p, s, m, r
+
+    def run_files(self, pairs, batch_size: int = 4, workers: int = 0, want_masks: bool = False,
+                  want_rle: bool = False, thresholds: Optional[Sequence] = None) -> Iterator:
+        """``predict_files`` and ``score_files`` from one forward pass: ``pairs`` of (image path, mask path) ->
+        ``(image path, (Hs, Ws), mask or None, runs or None, counts int64 [1 + 2T])`` per pair, in input order."""
+        thresholds = [self.threshold] if thresholds is None else [float(t) for t in thresholds]
+        post = want_masks or want_rle
+        for chunk, items in self._batches(pairs, self._decode_pair, batch_size, workers):
+            sizes = [it[0] for it in items]
+            probs = self.probs(self._inputs([it[:3] for it in items]))
+            res = self.post(probs, sizes, want_masks, want_rle) if post else [(None, None)] * len(items)
+            counts = self.score(probs, [it[3] for it in items], [it[4] for it in items], thresholds,
+                                count_host=not post)
+            for (p, _), s, (m, r), c in zip(chunk, sizes, res, counts):
+                yield p, s, m, r, c
+
+    def score_files(self, pairs, batch_size: int = 4, workers: int = 0,
+                    thresholds: Optional[Sequence] = None) -> Iterator:
+        """Yields ``(image path, (Hs, Ws), counts int64 [1 + 2T])`` per (image path, mask path) pair, in input
+        order: what the Dice coefficient of the full-size mask against the mask file is made of
+        (``ops.kernels.dice_iou``), for every threshold (default: the predictor's own)."""
+        for p, s, _, _, c in self.run_files(pairs, batch_size, workers, thresholds=thresholds):
+            yield p, s, c
+
+
+def load_truth(mask_path, size, image_path=None):
+    """The ground truth of one mask file at its own size, by the rule of ``BasicDataset.preprocess(mask,
+    mask.size, is_mask=True)``: the first channel; ``> 127`` when the maximum exceeds 1, else non-zero.  Returns
+    ``(uint8 [Hs, Ws], cut)`` with truth = ``array > cut``: a uint8 file as it is with ``cut`` 127 or 0, anything
+    else normalised to 0/1 with ``cut`` 0.  ``size = (Hs, Ws)`` is the image's."""
+    m = _load_image(Path(mask_path))
+    if (m.size[1], m.size[0]) != tuple(size):
+        raise ValueError(f"{image_path or mask_path}: the image is {size[1]}x{size[0]}, its mask {mask_path} "
+                         f"{m.size[0]}x{m.size[1]}")
+    a = np.asarray(m)
+    if a.ndim == 3:
+        a = a[..., 0]
+    big = bool(a.max(initial=0) > 1)
+    if a.dtype != np.uint8:
+        return ((a > 127) if big else (a > 0)).astype(np.uint8), 0
+    return np.ascontiguousarray(a), (127 if big else 0)
+
+
+def match_masks(files, masks_dir, suffix: str = "_mask") -> list:
+    """``(image, mask)`` per image file: the one file in ``masks_dir`` whose stem is the image's stem + ``suffix``.
+    Raises ``ValueError`` naming the stem when there is none or more than one."""
+    by_stem = {}
+    for f in sorted(os.listdir(masks_dir)):
+        if not f.startswith(".") and os.path.isfile(os.path.join(masks_dir, f)):
+            by_stem.setdefault(os.path.splitext(f)[0], []).append(os.path.join(masks_dir, f))
+    pairs = []
+    for p in files:
+        stem = Path(p).stem
+        m = by_stem.get(stem + suffix, [])
+        if len(m) != 1:
+            raise ValueError(f"{'no mask' if not m else 'several masks'} for {stem} in {masks_dir} "
+                             f"(looked for {stem + suffix}.*){': ' + ', '.join(m) if m else ''}")
+        pairs.append((p, m[0]))
+    return pairs
 
 
 def list_inputs(inputs) -> list:
@@ -254,9 +369,21 @@ def main(argv=None):
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
                     help="compute dtype (default bf16 on a GPU, fp32 on CPU; on a GPU fp32 runs the fp32 HIP engine)")
+    ap.add_argument("--score", default=None, metavar="MASKS_DIR",
+                    help="score the full-size masks against MASKS_DIR/<stem><suffix>.*: mean per-image Dice and IoU")
+    ap.add_argument("--mask-suffix", default="_mask", help="what a mask's stem adds to its image's")
+    ap.add_argument("--score-thresholds", type=float, nargs="+", default=None, metavar="T",
+                    help="score at these thresholds, at most 8 (default: --threshold)")
+    ap.add_argument("--score-csv", default=None, metavar="FILE",
+                    help="write img,height,width,threshold,truth,pred,inter,dice,iou per image and threshold")
     a = ap.parse_args(argv)
-    if not a.output and not a.rle:
-        ap.error("nothing to write: give --output DIR and / or --rle FILE.csv")
+    if not a.output and not a.rle and not a.score:
+        ap.error("nothing to write: give --output DIR and / or --rle FILE.csv (or --score MASKS_DIR)")
+    if (a.score_thresholds or a.score_csv) and not a.score:
+        ap.error("--score-thresholds and --score-csv need --score MASKS_DIR")
+    thresholds = a.score_thresholds or [a.threshold]
+    if len(thresholds) > 8:
+        ap.error(f"--score-thresholds takes at most 8 values, got {len(thresholds)}")
     path = a.load or (os.path.join(a.out_dir, "checkpoints", f"{a.checkpoint}.pth") if a.checkpoint else None)
     if not path:
         ap.error("no checkpoint: give -c NAME or -l PATH")
@@ -268,6 +395,14 @@ def main(argv=None):
     missing = [f for f in files if not os.path.isfile(f)]
     if missing:
         ap.error(f"input file not found: {missing[0]}")
+    pairs = None
+    if a.score:
+        if not os.path.isdir(a.score):
+            ap.error(f"--score: no such directory: {a.score}")
+        try:
+            pairs = match_masks(files, a.score, a.mask_suffix)
+        except ValueError as e:
+            ap.error(str(e))
 
     model = build_model(a.model)
     load_model_state(model, path)
@@ -276,10 +411,17 @@ def main(argv=None):
                      threshold=a.threshold, host_post=a.host_post)
     if a.output:
         os.makedirs(a.output, exist_ok=True)
-    rows = []
+    rows, scored = [], []
     t0 = time.perf_counter()
-    for p, _, mask, runs in pred.predict_files(files, a.batch_size, a.num_workers, want_masks=bool(a.output),
-                                               want_rle=bool(a.rle)):
+    if pairs is None:
+        results = ((p, s, m, r, None) for p, s, m, r in
+                   pred.predict_files(files, a.batch_size, a.num_workers, want_masks=bool(a.output), want_rle=bool(a.rle)))
+    else:
+        results = pred.run_files(pairs, a.batch_size, a.num_workers, want_masks=bool(a.output), want_rle=bool(a.rle),
+                                 thresholds=thresholds)
+    for p, size, mask, runs, counts in results:
+        if counts is not None:
+            scored.append((os.path.basename(p), size, counts))
         if a.output:
             from PIL import Image
             Image.fromarray(mask).save(os.path.join(a.output, Path(p).stem + "_mask.png"))
@@ -295,7 +437,33 @@ def main(argv=None):
     print(f"predicted {len(files)} files in {dt:.2f} s: {len(files) / dt:.1f} img/s, {pred.host_finished} finished on "
           f"the host (backend {pred.strat.compute.name}, dtype {pred.dtype}, post-processing "
           f"{'host' if pred.host_post else 'device'})")
-    return len(files), pred.host_finished
+    if pairs is None:
+        return len(files), pred.host_finished
+    return len(files), pred.host_finished, report_scores(scored, thresholds, a.score_csv)
+
+
+def report_scores(scored, thresholds, csv_path=None):
+    """``scored``: ``(name, (Hs, Ws), counts int64 [1 + 2T])`` per image.  Prints per threshold the mean over the
+    images of the per-image Dice coefficient and IoU (the Carvana score is the Dice column) and marks the
+    threshold with the best mean Dice; writes one CSV row per (image, threshold) when asked.  Returns
+    ``(mean dice [T], mean iou [T])``."""
+    from .ops.kernels import dice_iou
+    dice, iou = dice_iou(np.stack([c for _, _, c in scored]))                 # [N, T]
+    if csv_path:
+        os.makedirs(os.path.dirname(os.path.abspath(csv_path)), exist_ok=True)
+        with open(csv_path, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(("img", "height", "width", "threshold", "truth", "pred", "inter", "dice", "iou"))
+            for i, (name, (Hs, Ws), c) in enumerate(scored):
+                for t, thr in enumerate(thresholds):
+                    w.writerow((name, Hs, Ws, repr(float(thr)), int(c[0]), int(c[1 + 2 * t]), int(c[2 + 2 * t]),
+                                repr(float(dice[i, t])), repr(float(iou[i, t]))))
+    md, mi = dice.mean(0), iou.mean(0)
+    best = int(np.argmax(md))
+    for t, thr in enumerate(thresholds):
+        print(f"score threshold {float(thr):g}: dice {md[t]:.6f} iou {mi[t]:.6f} ({len(scored)} images)"
+              f"{'  <- best' if t == best and len(thresholds) > 1 else ''}")
+    return md, mi
 
 
 if __name__ == "__main__":

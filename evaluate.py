@@ -59,7 +59,13 @@ def main(argv=None):
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"],
                     help="compute dtype (default bf16 on a GPU, fp32 on CPU; on a GPU fp32 runs the fp32 HIP engine)")
     ap.add_argument("--seed", "-s", type=int, default=42)
+    ap.add_argument("--full-res", action="store_true",
+                    help="also score the held-out files of --data-dir the way the dataset is scored: mean per-image "
+                         "Dice of the thresholded mask at the source resolution (as predict.py --score)")
+    ap.add_argument("--threshold", type=float, default=0.5, help="mask threshold of --full-res")
     a = ap.parse_args(argv)
+    if a.full_res and a.synthetic:
+        ap.error("--full-res scores image files: give a --data-dir, not --synthetic")
     H, W = (a.img_size[0], a.img_size[-1])
     model = build_model(a.model)
     path = a.load or (os.path.join(a.out_dir, "checkpoints", f"{a.checkpoint}.pth") if a.checkpoint else None)
@@ -91,7 +97,20 @@ def main(argv=None):
     loss, dice = evaluate_strategy(strat, val_loader)
     print(f"backend {strat.compute.name} dtype {dtype}")
     print(f"val_loss {loss:.5f} dice {dice:.4f} ({len(val_set)} images, checkpoint {path})")
-    return loss, dice
+    if not a.full_res:
+        return loss, dice
+    # the files train.py held out (same listing, same split), at their own size: only the listing, no resident set
+    from distributedpytorch_amd.ops.kernels import dice_iou
+    from distributedpytorch_amd.predict import Predictor
+    ds = CarvanaDataset(os.path.join(a.data_dir, "train_hq"), os.path.join(a.data_dir, "train_masks"), newsize=(W, H))
+    _, held_out = split_dataset(ds, a.validation, seed=0)
+    pairs = [tuple(str(p) for p in ds._pairs[i]) for i in held_out.indices]
+    pred = Predictor(model, dev, (H, W), dtype=dtype, backend=a.backend, threshold=a.threshold)
+    counts = np.stack([c for _, _, c in pred.score_files(pairs, a.batch_size)]) if pairs else np.zeros((0, 3), np.int64)
+    d, i = dice_iou(counts)
+    full = (float(d.mean()), float(i.mean())) if len(pairs) else (float("nan"), float("nan"))
+    print(f"full_res dice {full[0]:.6f} iou {full[1]:.6f} ({len(pairs)} images, threshold {a.threshold:g})")
+    return loss, dice, full
 
 
 if __name__ == "__main__":

@@ -20,6 +20,10 @@ CSRC = ROOT / "csrc"
 OUT = ROOT / "distributedpytorch_amd" / "_C"
 BUILD = ROOT / "build" / "hip"
 ARCH = os.environ.get("DPA_ARCH", "gfx950")
+# Per-file flags, after the common ones.  predict_post.hip reproduces PIL's double sums (a rounded multiply, then
+# a rounded add) and says so with `#pragma clang fp contract(off)`; plain `-ffp-contract=fast` lets the backend
+# fuse them into an fma all the same.
+FILE_FLAGS = {"predict_post.hip": ["-ffp-contract=fast-honor-pragmas"]}
 
 
 def torch_lib_dir() -> Path:
@@ -43,7 +47,7 @@ def compile_one(src: Path, extra, verbose=False) -> Path:
         return obj
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-c", str(src), "-o", str(obj),
            "-I", str(CSRC), "-ffp-contract=fast", "-munsafe-fp-atomics", "-Wno-unused-result"]
-    cmd += extra.get("flags", [])
+    cmd += FILE_FLAGS.get(src.name, []) + extra.get("flags", [])
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
