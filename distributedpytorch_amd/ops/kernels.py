@@ -1939,3 +1939,145 @@ def prob_score(probs: torch.Tensor, truth: torch.Tensor, cut: torch.Tensor, thre
                             _p(hb), _p(hc), c_int(kh), _p(vb), _p(vc), c_int(kv), host_thr, c_int(T), _p(counts),
                             _p(work), c_ll(work.numel()), _stream(probs)), "prob_score")
     return counts
+
+
+# ---- mask cleaning (csrc/mask_clean.hip): largest component, hole filling -------------------------------------
+CLEAN_NAMES = ("largest", "fill")                    # canonical order, and the order in which they are applied
+
+
+def parse_clean(spec) -> str:
+    """``--clean``: ``none``, or names from ``largest`` and ``fill`` joined by ``+`` in any order -> the canonical
+    string (``fill+largest`` -> ``largest+fill``).  Raises ``ValueError`` naming an unknown or empty part."""
+    parts = [t.strip() for t in str(spec).split("+")]
+    if parts == ["none"]:
+        return "none"
+    for t in parts:
+        if t not in CLEAN_NAMES:
+            what = "an empty part" if not t else f"unknown part {t!r}"
+            raise ValueError(f"clean spec {str(spec)!r} has {what}: use none, or names from largest and fill "
+                             f"joined by +")
+    return "+".join(n for n in CLEAN_NAMES if n in parts)
+
+
+def _runs_2d(fg):
+    """Per-row maximal runs of a boolean ``[H, W]`` array in row-major order: (row, start, end exclusive)."""
+    import numpy as np
+    H, W = fg.shape
+    pad = np.zeros((H, W + 2), np.bool_)
+    pad[:, 1:-1] = fg
+    r, c = np.nonzero(pad[:, 1:] != pad[:, :-1])             # changes alternate start, end within a row
+    return r[0::2].astype(np.int64), c[0::2].astype(np.int64), c[1::2].astype(np.int64)
+
+
+def label_reference(fg, conn: int = 8):
+    """Connected components of the boolean set ``fg [H, W]`` with connectivity ``conn`` (8 or 4) in numpy: int32
+    ``[H, W]``, -1 off the set, else the smallest row-major index of the pixel's component.  Two passes over the
+    per-row runs: a run is united with the runs of the previous row it overlaps (widened by one pixel for
+    connectivity 8) in a union-find whose root is the smallest run number, i.e. the run that starts first."""
+    import numpy as np
+    assert conn in (4, 8), f"label_reference: connectivity 4 or 8, got {conn}"
+    fg = np.asarray(fg) != 0
+    assert fg.ndim == 2
+    H, W = fg.shape
+    out = np.full(H * W, -1, np.int32)
+    row, s, e = _runs_2d(fg)
+    if row.size == 0:
+        return out.reshape(H, W)
+    k, S = (1 if conn == 8 else 0), W + 3
+    # for run i the runs j of row[i] - 1 with e[j] > s[i] - k and s[j] < e[i] + k: a slice lo[i] .. hi[i] - 1
+    lo = np.searchsorted((row + 1) * S + e, row * S + s - k, side="right")
+    hi = np.searchsorted((row + 1) * S + s, row * S + e + k, side="left")
+    parent = list(range(row.size))
+    for i in np.flatnonzero(hi > lo).tolist():
+        for j in range(int(lo[i]), int(hi[i])):
+            a, b = i, j
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            while parent[b] != b:
+                parent[b] = parent[parent[b]]
+                b = parent[b]
+            if a < b:
+                parent[b] = a
+            elif b < a:
+                parent[a] = b
+    for i in range(len(parent)):                             # parents precede their children: one pass flattens
+        parent[i] = parent[parent[i]]
+    first = row * W + s                                      # a run's first pixel
+    lens = e - s
+    ends = np.cumsum(lens)
+    pix = np.repeat(first - (ends - lens), lens) + np.arange(int(ends[-1]))
+    out[pix] = np.repeat(first[np.asarray(parent)], lens).astype(np.int32)
+    return out.reshape(H, W)
+
+
+def clean_reference(mask, largest: bool = True, fill: bool = True, value: int = 255):
+    """The definition of mask cleaning, in numpy.  Foreground is every non-zero byte of ``mask [H, W]``.
+    ``largest``: keep the 8-connected component with the most pixels, on a tie the one whose first pixel in
+    row-major order comes first.  ``fill``, applied to that result: a background pixel that cannot reach the image
+    border through 4-connected background becomes foreground (removed components count as background).  Returns
+    (uint8 ``[H, W]`` of 0 / ``value``, int64 ``[3]`` = (foreground components before cleaning, foreground pixels
+    removed, pixels filled)); a stage that is off reports 0, and without ``largest`` the component count is 0."""
+    import numpy as np
+    keep = np.asarray(mask) != 0
+    assert keep.ndim == 2 and 1 <= int(value) <= 255
+    stats = np.zeros(3, np.int64)
+    if largest:
+        lab = label_reference(keep, 8).reshape(-1)
+        areas = np.bincount(lab[lab >= 0], minlength=1)
+        if areas.max() > 0:
+            stats[0] = np.count_nonzero(areas)
+            win = int(np.argmax(areas))                      # the first maximum: the smallest root
+            stats[1] = int(areas.sum() - areas[win])
+            keep = (lab == win).reshape(keep.shape)
+    if fill:
+        lab = label_reference(~keep, 4)
+        rim = np.concatenate([lab[0], lab[-1], lab[:, 0], lab[:, -1]])
+        open_ = np.zeros(lab.size + 1, np.bool_)             # the last entry takes the -1 of foreground pixels
+        open_[rim] = True
+        holes = (lab >= 0) & ~open_[lab]
+        stats[2] = int(holes.sum())
+        keep = keep | holes
+    return keep.astype(np.uint8) * np.uint8(value), stats
+
+
+def mask_clean(masks: torch.Tensor, largest: bool, fill: bool, value: int = 255):
+    """``clean_reference`` on the device for ``masks`` uint8 ``[B, H, W]`` -> (``cleaned`` uint8 ``[B, H, W]`` of
+    0 / ``value``, ``stats`` int32 ``[B, 3]``); ``masks`` is not modified.  Returns None, without launching, for an
+    image size the launcher refuses (``dpa_mask_clean_work`` is 0): the caller then cleans on the host."""
+    _u8(masks, "mask_clean.masks")
+    assert masks.dim() == 3 and min(masks.shape) > 0 and (largest or fill) and 1 <= int(value) <= 255
+    B, H, W = masks.shape
+    L = _lib.lib()
+    per = int(L.dpa_mask_clean_work(c_int(H), c_int(W)))
+    if per == 0:
+        return None
+    dst = torch.empty_like(masks)
+    stats = torch.empty(B, 3, dtype=torch.int32, device=masks.device)
+    work = torch.empty(B * per, dtype=torch.int32, device=masks.device)
+    flags = (1 if largest else 0) | (2 if fill else 0)
+    _check(L.dpa_mask_clean(_p(masks), c_int(B), c_int(H), c_int(W), _p(dst), c_int(flags), c_int(int(value)),
+                            _p(stats), _p(work), c_ll(work.numel()), _stream(masks)), "mask_clean")
+    return dst, stats
+
+
+def mask_score(masks: torch.Tensor, truth: torch.Tensor, cut: torch.Tensor):
+    """``masks`` and ``truth`` uint8 ``[B, H, W]``, ``cut`` int32 ``[B]`` -> int64 ``[B, 3]`` on the device =
+    (truth, pred, inter): pixels with ``truth > cut[b]``, with ``masks != 0``, and with both.  Returns None,
+    without launching, for an image size the launcher refuses."""
+    _u8(masks, "mask_score.masks")
+    _u8(truth, "mask_score.truth")
+    assert cut.dtype == torch.int32 and cut.is_contiguous() and cut.device == masks.device, \
+        f"mask_score.cut: need a contiguous int32 tensor on {masks.device}, got {cut.dtype} on {cut.device}"
+    assert masks.dim() == 3 and masks.shape == truth.shape and masks.device == truth.device and min(masks.shape) > 0
+    assert cut.dim() == 1 and cut.numel() == masks.shape[0]
+    B, H, W = masks.shape
+    L = _lib.lib()
+    blocks = int(L.dpa_mask_score_blocks(c_int(H), c_int(W)))
+    if blocks == 0:
+        return None
+    counts = torch.empty(B, 3, dtype=torch.int64, device=masks.device)
+    work = torch.empty(B * blocks * 3, dtype=torch.int32, device=masks.device)
+    _check(L.dpa_mask_score(_p(masks), _p(truth), _p(cut), c_int(B), c_int(H), c_int(W), _p(counts), _p(work),
+                            c_ll(work.numel()), _stream(masks)), "mask_score")
+    return counts

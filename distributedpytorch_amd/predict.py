@@ -26,6 +26,13 @@ to the image; per group of equal source sizes one ``dpa_prob_score`` launch resi
 thresholds at once) and counts truth, predicted and common pixels in registers, so no mask exists on the device
 and a few integers per image come back.  ``ops.kernels.score_reference`` (PIL + numpy) defines the counts and is
 the host path.
+
+``clean`` (``--clean``: ``largest``, ``fill`` or ``largest+fill``) cleans every mask between the threshold and the
+run lengths: the largest 8-connected component, then the holes of what is kept filled.  ``dpa_mask_clean``
+(csrc/mask_clean.hip) labels the full-size masks on the device, so still only run lists, three stats per image and
+the requested masks come back; scoring then goes mask -> clean -> ``dpa_mask_score`` per threshold, since a cleaned
+mask cannot be counted in registers straight from the probabilities.  ``ops.kernels.clean_reference`` (numpy) defines
+the result and is the host path.  With ``none`` nothing of this runs.
 """
 from __future__ import annotations
 
@@ -63,10 +70,13 @@ class Predictor:
     """Eval-mode forward of ``model`` at ``img_size = (H, W)`` plus the post-processing to source-size masks.
 
     ``host_post`` forces the host post-processing; ``rle_cap`` is the capacity of one device run list (default
-    ``4 * source height``; a list that overflows it is finished on the host)."""
+    ``4 * source height``; a list that overflows it is finished on the host); ``clean`` is a ``--clean`` spec
+    (``ops.kernels.parse_clean``): masks, run lists and scores are then those of the cleaned masks, and
+    ``clean_stats`` sums (components before cleaning, pixels removed, pixels filled) over the files."""
 
     def __init__(self, model, device, img_size, dtype: Optional[str] = None, backend: str = "auto",
-                 threshold: float = 0.5, host_post: bool = False, rle_cap: Optional[int] = None):
+                 threshold: float = 0.5, host_post: bool = False, rle_cap: Optional[int] = None,
+                 clean: str = "none"):
         from .config import TrainConfig
         from .trainer import SingleDevice
         self.device = torch.device(device)
@@ -82,6 +92,13 @@ class Predictor:
         self.rle_cap = None if rle_cap is None else int(rle_cap)
         assert self.rle_cap is None or self.rle_cap >= 1, "rle_cap must be positive"
         self.host_finished = 0          # files whose mask / run list the host path produced
+        from .ops.kernels import parse_clean
+        self.clean = parse_clean(clean)
+        self.largest, self.fill = (n in self.clean.split("+") for n in ("largest", "fill"))
+        # over the files finished: (components before cleaning, pixels removed, pixels filled); the files that lost
+        # a component and the components they lost
+        self.clean_stats = np.zeros(3, np.int64)
+        self.clean_files = self.clean_removed = 0
 
     # ---- decode (worker threads) ------------------------------------------------------------------------
     def _decode(self, path):
@@ -133,10 +150,26 @@ class Predictor:
         assert p.dim() == 4 and p.shape[1] == 1, f"probs: expected [B, 1, h, w], got {tuple(p.shape)}"
         return p.to(torch.float32).reshape(p.shape[0], p.shape[2], p.shape[3]).contiguous()
 
+    def _add_clean_stats(self, stats) -> None:
+        stats = np.asarray(stats, np.int64).reshape(-1, 3)
+        self.clean_stats += stats.sum(0)
+        self.clean_files += int((stats[:, 1] > 0).sum())
+        self.clean_removed += int(np.maximum(stats[:, 0] - 1, 0).sum())
+
+    def _host_clean(self, m: np.ndarray, count: bool = True) -> np.ndarray:
+        """``clean_reference`` by the predictor's spec; ``count``: add the stats to ``clean_stats``."""
+        if self.clean == "none":
+            return m
+        from .ops.kernels import clean_reference
+        m, stats = clean_reference(m, self.largest, self.fill, 255)
+        if count:
+            self._add_clean_stats(stats)
+        return m
+
     def _host_finish(self, prob: np.ndarray, size, want_masks: bool, want_rle: bool):
         from .ops.kernels import rle_reference
         self.host_finished += 1
-        m = host_mask(prob, size, self.threshold)
+        m = self._host_clean(host_mask(prob, size, self.threshold))
         return (m if want_masks else None), (rle_reference(m) if want_rle else None)
 
     def post(self, probs: torch.Tensor, sizes: Sequence, want_masks: bool = True, want_rle: bool = True):
@@ -159,15 +192,22 @@ class Predictor:
             if not K.prob_to_mask_u8(sel, masks, self.threshold, 255):
                 todo += idx
                 continue
+            stats = None
+            if self.clean != "none":
+                cleaned = K.mask_clean(masks, self.largest, self.fill, 255)
+                if cleaned is None:         # a size the clean launcher refuses: the host finishes these
+                    todo += idx
+                    continue
+                masks, stats = cleaned
             runs = counts = None
             if want_rle:
                 runs, counts = K.mask_rle(masks, self.rle_cap or 4 * Hs)
-            launched.append((idx, masks, runs, counts))
+            launched.append((idx, masks, runs, counts, stats))
         if want_rle and launched:
             # two small downloads for the whole batch: the counts, then the used prefixes of the run lists
-            counts = torch.cat([c for _, _, _, c in launched]).cpu().numpy()
+            counts = torch.cat([c for _, _, _, c, _ in launched]).cpu().numpy()
             parts, k = [], 0
-            for idx, _, runs, _ in launched:
+            for idx, _, runs, _, _ in launched:
                 for j in range(len(idx)):
                     n = int(counts[k + j])
                     if n <= runs.shape[1]:
@@ -175,7 +215,7 @@ class Predictor:
                 k += len(idx)
             flat = torch.cat(parts).cpu().numpy() if parts else np.zeros((0, 2), np.int32)
             k = pos = 0
-            for idx, _, runs, _ in launched:
+            for idx, _, runs, _, _ in launched:
                 for j, i in enumerate(idx):
                     n = int(counts[k + j])
                     if n <= runs.shape[1]:
@@ -184,7 +224,11 @@ class Predictor:
                     else:                   # overflow: nothing behind cap was written; the host encodes
                         todo.append(i)
                 k += len(idx)
-        for idx, masks, _, _ in launched:
+        if self.clean != "none" and launched:
+            stats = torch.cat([s for _, _, _, _, s in launched]).cpu().numpy()
+            keep = [i not in todo for idx, _, _, _, _ in launched for i in idx]     # the host counts its own
+            self._add_clean_stats(stats[keep])
+        for idx, masks, _, _, _ in launched:
             host = masks.cpu().numpy() if want_masks else None
             for j, i in enumerate(idx):
                 if i in todo:
@@ -209,6 +253,8 @@ class Predictor:
         from .ops import kernels as K
         B, T = probs.shape[0], len(thresholds)
         assert len(truths) == len(cuts) == B and 1 <= T <= K.SCORE_TMAX
+        if self.clean != "none":
+            return self._score_cleaned(probs, truths, cuts, thresholds, count_host)
         out = np.empty((B, 1 + 2 * T), np.int64)
         todo, launched = list(range(B)), []
         if not self.host_post:
@@ -233,6 +279,57 @@ class Predictor:
                     probs.index_select(0, torch.tensor(todo, device=probs.device))).cpu().numpy()
             for j, i in enumerate(todo):
                 out[i] = K.score_reference(host[j], truths[i], int(cuts[i]), thresholds)
+            if count_host:
+                self.host_finished += len(todo)
+        return out
+
+    def _score_cleaned(self, probs, truths, cuts, thresholds, count_host: bool) -> np.ndarray:
+        """``score`` of the CLEANED masks.  A cleaned mask cannot be counted in registers straight from the
+        probabilities, so per group of equal source sizes and per threshold: ``dpa_prob_to_mask_u8`` ->
+        ``dpa_mask_clean`` -> ``dpa_mask_score``; still only the counts come back.  The host path is ``host_mask``
+        -> ``clean_reference`` -> numpy counts.  ``count_host`` (``post`` did not run on these files): the files the
+        host finishes are counted, and ``clean_stats`` takes the stats of the first threshold."""
+        from .ops import kernels as K
+        B, T = probs.shape[0], len(thresholds)
+        out = np.empty((B, 1 + 2 * T), np.int64)
+        todo, launched = list(range(B)), []
+        if not self.host_post:
+            groups = {}
+            for i, t in enumerate(truths):
+                groups.setdefault(tuple(t.shape), []).append(i)
+            todo = []
+            for (Hs, Ws), idx in groups.items():
+                sel = probs if len(idx) == B else probs.index_select(0, torch.tensor(idx, device=probs.device))
+                truth = torch.from_numpy(np.stack([truths[i] for i in idx])).to(probs.device, non_blocking=True)
+                cut = torch.tensor([int(cuts[i]) for i in idx], dtype=torch.int32).to(probs.device, non_blocking=True)
+                masks = torch.empty(len(idx), Hs, Ws, dtype=torch.uint8, device=probs.device)
+                per_t, stats0 = [], None
+                for t, thr in enumerate(thresholds):
+                    cleaned = K.mask_clean(masks, self.largest, self.fill, 255) \
+                        if K.prob_to_mask_u8(sel, masks, float(thr), 255) else None
+                    counts = None if cleaned is None else K.mask_score(cleaned[0], truth, cut)
+                    if counts is None:      # refused for this size at the first threshold already
+                        break
+                    per_t.append(counts)
+                    stats0 = cleaned[1] if t == 0 else stats0
+                if len(per_t) < T:
+                    todo += idx
+                else:
+                    launched.append((idx, torch.cat([per_t[0][:, :1]] + [c[:, 1:] for c in per_t], 1), stats0))
+            if launched:
+                out[[i for idx, _, _ in launched for i in idx]] = torch.cat([c for _, c, _ in launched]).cpu().numpy()
+                if count_host:
+                    self._add_clean_stats(torch.cat([s for _, _, s in launched]).cpu().numpy())
+        if todo:
+            todo = sorted(todo)
+            host = (probs if len(todo) == B else
+                    probs.index_select(0, torch.tensor(todo, device=probs.device))).cpu().numpy()
+            for j, i in enumerate(todo):
+                truth = np.asarray(truths[i]) > int(cuts[i])
+                out[i, 0] = int(truth.sum())
+                for t, thr in enumerate(thresholds):
+                    m = self._host_clean(host_mask(host[j], truth.shape, float(thr)), count=count_host and t == 0) != 0
+                    out[i, 1 + 2 * t], out[i, 2 + 2 * t] = int(m.sum()), int((m & truth).sum())
             if count_host:
                 self.host_finished += len(todo)
         return out
@@ -344,6 +441,15 @@ def list_inputs(inputs) -> list:
     return out
 
 
+def _clean_spec(text: str) -> str:
+    """``--clean``: the canonical spec string (``fill+largest`` -> ``largest+fill``)."""
+    from .ops.kernels import parse_clean
+    try:
+        return parse_clean(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def rle_string(runs) -> str:
     return " ".join(str(int(v)) for v in np.asarray(runs).reshape(-1))
 
@@ -364,6 +470,10 @@ def main(argv=None):
     ap.add_argument("--num-workers", type=int, default=0, help="decode threads (0: min(8, cpus); at most 16)")
     ap.add_argument("--host-post", action="store_true",
                     help="post-process on the host (PIL + numpy): the fallback made selectable, for comparison")
+    ap.add_argument("--clean", type=_clean_spec, default="none", metavar="SPEC",
+                    help="clean every mask after the threshold: none, or largest (keep the largest 8-connected "
+                         "component) and fill (fill enclosed holes) joined by +; masks, run lists and scores are "
+                         "those of the cleaned masks")
     ap.add_argument("--out-dir", default=".", help="where checkpoints/ lives")
     ap.add_argument("--model", default="unet")
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
@@ -408,7 +518,7 @@ def main(argv=None):
     load_model_state(model, path)
     dev = "cuda:0" if torch.cuda.is_available() else "cpu"
     pred = Predictor(model, dev, (a.img_size[0], a.img_size[-1]), dtype=a.dtype, backend=a.backend,
-                     threshold=a.threshold, host_post=a.host_post)
+                     threshold=a.threshold, host_post=a.host_post, clean=a.clean)
     if a.output:
         os.makedirs(a.output, exist_ok=True)
     rows, scored = [], []
@@ -437,6 +547,9 @@ def main(argv=None):
     print(f"predicted {len(files)} files in {dt:.2f} s: {len(files) / dt:.1f} img/s, {pred.host_finished} finished on "
           f"the host (backend {pred.strat.compute.name}, dtype {pred.dtype}, post-processing "
           f"{'host' if pred.host_post else 'device'})")
+    if pred.clean != "none":
+        print(f"cleaned ({pred.clean}): {pred.clean_removed} components removed "
+              f"from {pred.clean_files} files, {int(pred.clean_stats[2])} pixels filled")
     if pairs is None:
         return len(files), pred.host_finished
     return len(files), pred.host_finished, report_scores(scored, thresholds, a.score_csv)

@@ -4,6 +4,7 @@ run-length CSV (``img,rle_mask``) of the Carvana scoring.
 
     python3 predict.py -c singleGPU --input data/test_hq --output masks/ --rle submission.csv
     python3 predict.py -l checkpoints/DDP.pth --input a.jpg b.jpg --rle out.csv --img-size 512 -b 32
+    python3 predict.py -c singleGPU --input data/test_hq --rle submission.csv --clean largest+fill
 
 On a GPU the up-scale to the source size, the threshold and the run-length encoding run as HIP kernels
 (csrc/predict_post.hip), bit-equal to the host path (PIL + numpy) that ``--host-post`` selects and a CPU-only
