@@ -74,6 +74,8 @@ class TrainConfig:
     comm_timeout: float = 1800.0                     # process-group (RCCL/gloo) collective timeout, seconds
     nan_policy: str = "raise"                        # non-finite loss: raise | warn | ignore
     progress: Optional[bool] = None                  # tqdm bars (reference); None = only on a terminal
+    clip_grad_norm: float = 0.0                      # clip the global gradient norm to C (0 = off, inf = measure)
+    ema_decay: float = 0.0                           # EMA of the parameters, decay D (0 = off); <method>_ema.pth
 
     def to_dict(self):
         return asdict(self)
@@ -173,6 +175,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--progress", dest="progress", action="store_true", default=None,
                    help="tqdm progress bars for training images and validation batches (default: on a terminal)")
     p.add_argument("--no-progress", dest="progress", action="store_false")
+    p.add_argument("--clip-grad-norm", type=float, default=0.0, metavar="C",
+                   help="clip the global gradient norm to C inside the fused optimizer step (clip_grad_norm_'s rule; "
+                        "0 = off, inf = only measure); the train log gains gnorm, the JSONL grad_norm / clip_coef. "
+                        "singleGPU, DP and DDP")
+    p.add_argument("--ema-decay", type=float, default=0.0, metavar="D",
+                   help="keep an exponential moving average of the parameters in the optimizer step, decay "
+                        "min(D, (1 + step) / (10 + step)) (0 = off): validated every epoch next to the live weights "
+                        "and saved as checkpoints/<method>_ema.pth. singleGPU, DP and DDP")
     return p
 
 
@@ -195,6 +205,10 @@ def parse_args(argv=None) -> TrainConfig:
             raise SystemExit(f"--aug-{m} {v}: a magnitude cannot be negative")
         if not 0.0 <= v < float("inf"):                      # nan, inf
             raise SystemExit(f"--aug-{m} {v}: a magnitude must be finite")
+    if not a.clip_grad_norm >= 0.0:                              # negative, nan
+        raise SystemExit(f"--clip-grad-norm {a.clip_grad_norm}: a maximum norm is positive (0 = off, inf = measure)")
+    if not 0.0 <= a.ema_decay < 1.0:
+        raise SystemExit(f"--ema-decay {a.ema_decay}: a decay lies in [0, 1) (0 = off)")
     size = a.img_size
     img_size = (size[0], size[0]) if len(size) == 1 else (size[0], size[1])
     cfg = TrainConfig(
@@ -210,7 +224,8 @@ def parse_args(argv=None) -> TrainConfig:
         comm_overlap=a.comm_overlap, global_dice=a.global_dice,
         loss_scale_by_batch=a.loss_scale_by_batch, max_steps=a.max_steps, num_workers=a.num_workers,
         log_every=a.log_every, resume=a.resume, profile=a.profile, trace_ranges=a.trace_ranges, cuda_graph=a.cuda_graph,
-        debug_sync=a.debug_sync, watchdog=a.watchdog, comm_timeout=a.comm_timeout, nan_policy=a.nan_policy, progress=a.progress)
+        debug_sync=a.debug_sync, watchdog=a.watchdog, comm_timeout=a.comm_timeout, nan_policy=a.nan_policy, progress=a.progress,
+        clip_grad_norm=a.clip_grad_norm, ema_decay=a.ema_decay)
     return cfg
 
 

@@ -16,12 +16,16 @@ MI355X design:
 """
 from __future__ import annotations
 
+import contextlib
+import logging
 import math
 from typing import Iterable, List, Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
+
+log = logging.getLogger("dpa")
 
 
 def _hip_available() -> bool:
@@ -125,10 +129,27 @@ class FusedAdam(torch.optim.Optimizer):
 
     Several spaces occur when a single process owns parameters on several devices (``-t DP``
     replicas, single-process ``-t MP`` stages); each device then runs its own fused update.
+
+    Two options, both off by default (the step is then exactly the plain one, same launches):
+
+    * ``clip_grad_norm=C`` (0 = off, ``inf`` = measure only): per space, the global gradient norm is
+      reduced on the device (``ops.grad_sumsq``: fp64, fixed order, deterministic) and the Adam kernel
+      multiplies the gradient by ``coef = min(1, C / (norm + 1e-6))`` (``clip_grad_norm_``'s rule) as it
+      reads it.  ``space.grad`` is NOT rescaled in place: after ``step()`` it still holds the raw
+      gradient.  Nothing is read on the host; :meth:`grad_norm` reads the last step's values (a sync).
+    * ``ema_decay=D`` (0 = off): an exponential moving average of the parameters, updated in the same
+      pass, ``ema += (1 - d_t) (p_new - ema)`` with ``d_t = min(D, (1 + t) / (10 + t))`` at step ``t``
+      (a bare 0.999 would not leave the initial weights in a 20-step epoch).  :meth:`swap_ema`
+      evaluates with it, :meth:`ema_state_dict` exports it, ``state_dict()`` carries it.
     """
 
     def __init__(self, spaces, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 use_kernel: Optional[bool] = None):
+                 use_kernel: Optional[bool] = None, clip_grad_norm: float = 0.0, ema_decay: float = 0.0):
+        clip_grad_norm, ema_decay = float(clip_grad_norm), float(ema_decay)
+        if not clip_grad_norm >= 0.0:
+            raise ValueError(f"clip_grad_norm {clip_grad_norm}: a maximum norm is positive (0 = off, inf = measure)")
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay {ema_decay}: a decay lies in [0, 1) (0 = off)")
         if isinstance(spaces, FlatParameterSpace):
             spaces = [spaces]
         self.spaces: List[FlatParameterSpace] = list(spaces)
@@ -142,6 +163,34 @@ class FusedAdam(torch.optim.Optimizer):
         self.device_state = False
         self._dev_state: List[torch.Tensor] = []
         self._dev_lr = None
+        # clip / EMA state, allocated only when the feature is on: per space one fp64 aux block
+        # ({sumsq, norm, coef, 1 - d_t, ...}; coef starts at 1), one fp64 slab for the norm's block partials
+        # (GPU spaces), one fp32 EMA buffer initialised from the parameters
+        self.clip_grad_norm, self.ema_decay = clip_grad_norm, ema_decay
+        self.clip, self.ema_on = clip_grad_norm > 0.0, ema_decay > 0.0
+        self._aux: List[torch.Tensor] = []
+        self._slab: List[Optional[torch.Tensor]] = []
+        self.ema: List[torch.Tensor] = []
+        self._ema_stale = False
+        if self.clip or self.ema_on:
+            from .ops import AUX_LEN
+            for s in self.spaces:
+                a = torch.zeros(AUX_LEN, dtype=torch.float64, device=s.data.device)
+                a[2] = 1.0
+                self._aux.append(a)
+        if self.clip:
+            for s in self.spaces:
+                slab = None
+                if s.data.is_cuda:
+                    from . import ops
+                    slab = torch.zeros(max(1, ops.grad_sumsq_blocks(s.numel)), dtype=torch.float64,
+                                       device=s.data.device)
+                self._slab.append(slab)
+        if self.ema_on:
+            self.ema = [s.data.detach().clone() for s in self.spaces]
+
+    def _use_kernel(self, s) -> bool:
+        return s.data.is_cuda if self.use_kernel is None else self.use_kernel
 
     def enable_device_state(self):
         """Keep (step, lr, bias corrections) in a per-space fp64 device block that the step kernel
@@ -158,6 +207,13 @@ class FusedAdam(torch.optim.Optimizer):
         for st in self._dev_state:
             st.copy_(torch.tensor([float(self.step_count), lr, 0.0, 0.0], dtype=torch.float64))
         self._dev_lr = lr
+        if self.ema_on:
+            # the aux block's per-step EMA weight as of the current step (the tick kernel rewrites it from
+            # the step count before every update, so this only keeps the block consistent with the host)
+            from .ops import ema_decay_at
+            w = 1.0 - ema_decay_at(self.ema_decay, max(self.step_count, 1))
+            for a in self._aux:
+                a[3:4].copy_(torch.tensor([w], dtype=torch.float64))
 
     @property
     def space(self) -> FlatParameterSpace:
@@ -176,6 +232,9 @@ class FusedAdam(torch.optim.Optimizer):
         lr, eps, wd = g["lr"], g["eps"], g["weight_decay"]
         bc1 = 1 - b1 ** self.step_count
         bc2 = 1 - b2 ** self.step_count
+        if self.clip or self.ema_on:
+            self._step_x(lr, b1, b2, eps, wd, bc1, bc2)
+            return loss
         if self.device_state:
             from . import ops
             if lr != self._dev_lr and not _capturing(self.spaces[0].data):
@@ -197,12 +256,94 @@ class FusedAdam(torch.optim.Optimizer):
                 adam_reference(s.data, s.grad, m, v, lr, b1, b2, eps, wd, bc1, bc2)
         return loss
 
+    def _step_x(self, lr, b1, b2, eps, wd, bc1, bc2):
+        """The step with clipping and / or the EMA on: per space the norm (if clipping), then the extended Adam."""
+        from . import ops
+        if self.device_state and lr != self._dev_lr and not _capturing(self.spaces[0].data):
+            self.step_count -= 1
+            self.sync_device_state()
+            self.step_count += 1
+        d_t = ops.ema_decay_at(self.ema_decay, self.step_count) if self.ema_on else 0.0
+        for i, (s, m, v) in enumerate(zip(self.spaces, self.exp_avg, self.exp_avg_sq)):
+            s.touch()
+            aux = self._aux[i]
+            e = self.ema[i] if self.ema_on else None
+            if self.device_state:
+                if self.clip:
+                    ops.grad_sumsq(s.grad, aux, self.clip_grad_norm, self._slab[i])
+                ops.adam_step_x_dev(s.data, s.grad, m, v, self._dev_state[i], aux, beta1=b1, beta2=b2, eps=eps,
+                                    weight_decay=wd, ema=e, clip=self.clip, ema_decay=self.ema_decay)
+            elif self._use_kernel(s):
+                if self.clip:
+                    ops.grad_sumsq(s.grad, aux, self.clip_grad_norm, self._slab[i])
+                ops.adam_step_x(s.data, s.grad, m, v, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, bc1=bc1,
+                                bc2=bc2, ema=e, aux=aux if self.clip else None, ema_decay=d_t)
+            else:
+                if self.clip:
+                    aux[0], aux[1], aux[2] = clip_coef_reference(s.grad, self.clip_grad_norm)
+                adam_x_reference(s.data, s.grad, m, v, lr, b1, b2, eps, wd, bc1, bc2,
+                                 coef=aux[2] if self.clip else None, ema=e, ema_decay=d_t)
+
+    def grad_norm(self):
+        """``(norm, coef)`` of the last step in space 0: the gradient's global norm before clipping and the
+        factor applied.  Reads the device (a synchronisation): call it where the host waits anyway.  ``None``
+        when clipping is off."""
+        if not self.clip:
+            return None
+        a = self._aux[0].detach().cpu()
+        return float(a[1]), float(a[2])
+
+    @torch.no_grad()
+    def ema_state_dict(self, model: nn.Module):
+        """``model.state_dict()`` with every parameter replaced by its moving average (buffers, e.g. BatchNorm
+        running statistics, are the live model's)."""
+        if not self.ema_on:
+            raise RuntimeError("ema_state_dict: the optimizer keeps no EMA (ema_decay = 0)")
+        sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        done = set()
+        for s, e in zip(self.spaces, self.ema):
+            for name, p, o, n in zip(s.names, s.params, s.offsets, s.numels):
+                if name in sd and name not in done:       # replicas hold the same names and values
+                    sd[name] = e[o:o + n].view_as(p).to(sd[name].device, copy=True)
+                    done.add(name)
+        return sd
+
+    @torch.no_grad()
+    def _exchange_ema(self):
+        for s, e in zip(self.spaces, self.ema):
+            tmp = s.data.clone()
+            s.data.copy_(e)
+            e.copy_(tmp)
+            s.touch()
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Inside the block the model's parameters are the moving averages (and ``ema`` holds the live ones);
+        on exit they are exchanged back, bit for bit."""
+        if not self.ema_on:
+            raise RuntimeError("swap_ema: the optimizer keeps no EMA (ema_decay = 0)")
+        self._exchange_ema()
+        try:
+            yield self
+        finally:
+            self._exchange_ema()
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """Restart the moving averages from the current parameters."""
+        for s, e in zip(self.spaces, self.ema):
+            e.copy_(s.data)
+        self._ema_stale = False
+
     def state_dict(self):
-        return {"step": self.step_count,
-                "exp_avg": [m.detach().cpu() for m in self.exp_avg],
-                "exp_avg_sq": [v.detach().cpu() for v in self.exp_avg_sq],
-                "names": [s.names for s in self.spaces],
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        sd = {"step": self.step_count,
+              "exp_avg": [m.detach().cpu() for m in self.exp_avg],
+              "exp_avg_sq": [v.detach().cpu() for v in self.exp_avg_sq],
+              "names": [s.names for s in self.spaces],
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        if self.ema_on:
+            sd["ema"] = [e.detach().cpu() for e in self.ema]
+        return sd
 
     def load_state_dict(self, sd):
         # the moments are flat buffers matched by position: refuse a state whose parameter layout
@@ -224,6 +365,20 @@ class FusedAdam(torch.optim.Optimizer):
             v.copy_(src)
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
+        if self.ema_on:              # (a saved "ema" is ignored when this run keeps none)
+            saved_ema = sd.get("ema")
+            if saved_ema is not None:
+                if len(saved_ema) != len(self.ema) or any(
+                        tuple(a.shape) != tuple(b.shape) for a, b in zip(self.ema, saved_ema)):
+                    raise ValueError("saved EMA buffers do not match this run's flat parameter spaces")
+                for e, src in zip(self.ema, saved_ema):
+                    e.copy_(src)
+                self._ema_stale = False
+            else:
+                log.warning("optimizer state holds no EMA (saved with --ema-decay off): the moving average "
+                            "restarts from the loaded parameters")
+                self.reset_ema()
+                self._ema_stale = True       # strategies that replicate parameters after a load repeat this
         if self.device_state:
             self.sync_device_state()
 
@@ -240,6 +395,31 @@ def adam_reference(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2):
     v.mul_(b2).addcmul_(grad, grad, value=1 - b2)
     denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
     p.addcdiv_(m, denom, value=-lr / bc1)
+
+
+@torch.no_grad()
+def clip_coef_reference(g, max_norm):
+    """``(sumsq, norm, coef)`` of a flat gradient as Python floats, all in fp64: the global norm
+    ``sqrt((g.double()**2).sum())`` and ``coef = min(1, max_norm / (norm + 1e-6))``
+    (``torch.nn.utils.clip_grad_norm_``'s rule).  ``max_norm = inf`` gives 1; a non-finite sum gives NaN, so
+    the step poisons the parameters and ``--nan-policy`` sees it."""
+    sumsq = float((g.double() ** 2).sum())
+    norm = math.sqrt(sumsq) if sumsq >= 0.0 else float("nan")
+    if not math.isfinite(sumsq):
+        return sumsq, norm, float("nan")
+    return sumsq, norm, min(1.0, float(max_norm) / (norm + 1e-6))
+
+
+@torch.no_grad()
+def adam_x_reference(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2, coef=None, ema=None, ema_decay=0.0):
+    """:func:`adam_reference` on the gradient ``coef * g`` (``coef``: fp64, cast to fp32; ``g`` is left as it
+    is), then ``ema += (1 - ema_decay) * (p_new - ema)`` on the updated parameter."""
+    if coef is not None:
+        c32 = torch.as_tensor(coef, dtype=torch.float64).to(device=g.device, dtype=torch.float32)
+        g = g * c32
+    adam_reference(p, g, m, v, lr, b1, b2, eps, wd, bc1, bc2)
+    if ema is not None:
+        ema.add_(p - ema, alpha=1.0 - ema_decay)
 
 
 def make_plateau(optimizer, patience: int = 2):

@@ -87,6 +87,14 @@ class Strategy:
         """Parameters were overwritten in place (resume / load): kernels re-pack their weights."""
         for sp in self.spaces():
             sp.touch()
+        self._restart_stale_ema()
+
+    def _restart_stale_ema(self):
+        """A resume from a state saved without an EMA: the average restarts from the parameters as loaded (and,
+        for replicas, as replicated)."""
+        opt = getattr(self, "optimizer", None)
+        if getattr(opt, "_ema_stale", False):
+            opt.reset_ema()
 
     def optimizer_state_dict(self):
         """Optimizer state to checkpoint (collective for strategies whose state is sharded)."""
@@ -94,6 +102,20 @@ class Strategy:
 
     def load_optimizer_state_dict(self, sd):
         self.optimizer.load_state_dict(sd)
+
+
+def _optim_ext(cfg) -> dict:
+    """``FusedAdam``'s clipping / EMA arguments (``--clip-grad-norm``, ``--ema-decay``)."""
+    return dict(clip_grad_norm=cfg.clip_grad_norm, ema_decay=cfg.ema_decay)
+
+
+def _refuse_optim_ext_mp(cfg):
+    """``-t MP`` spreads the parameters over the stages: the global gradient norm and a gathered EMA checkpoint
+    need a cross-stage step that does not exist."""
+    if cfg.clip_grad_norm or cfg.ema_decay:
+        raise ValueError("--clip-grad-norm / --ema-decay are not available with -t MP: the parameters are spread "
+                         "over the pipeline stages, and the global gradient norm and the gathered EMA would need a "
+                         "cross-stage reduction that is not built; use singleGPU, DP or DDP")
 
 
 def _loss_scale(cfg, batch):
@@ -119,7 +141,8 @@ class SingleDevice(Strategy):
         self.model = model.to(self.device)
         self.space = FlatParameterSpace(self.model, device=self.device)
         self.compute = make_compute(self.model, cfg.backend, cfg.dtype)
-        self.optimizer = FusedAdam(self.space, lr=cfg.lr * self.lr_scale(), weight_decay=cfg.weight_decay)
+        self.optimizer = FusedAdam(self.space, lr=cfg.lr * self.lr_scale(), weight_decay=cfg.weight_decay,
+                                   **_optim_ext(cfg))
 
     def forward_loss(self, images, targets):
         S = self.compute.forward_partials(images, targets)
@@ -220,7 +243,7 @@ class DPStrategy(Strategy):
         self.reducer = self.dp.reducer
         self.device = self.dp.devices[0]
         self.model = self.dp.module
-        self.optimizer = FusedAdam(self.dp.spaces, lr=cfg.lr, weight_decay=cfg.weight_decay)
+        self.optimizer = FusedAdam(self.dp.spaces, lr=cfg.lr, weight_decay=cfg.weight_decay, **_optim_ext(cfg))
 
     def set_train(self, mode: bool):
         for r in self.dp.replicas:
@@ -234,6 +257,7 @@ class DPStrategy(Strategy):
     def after_load(self):
         # a resume loads replica 0 only; replicate its parameters and buffers to the others
         self.dp.sync_from_replica0()
+        self._restart_stale_ema()
 
     def state_dict(self):
         self.dp.sync_buffers()
@@ -259,6 +283,7 @@ class PipelineLocalStrategy(Strategy):
 
     def __init__(self, cfg, model, devices):
         super().__init__(cfg)
+        _refuse_optim_ext_mp(cfg)
         H, W = cfg.img_size
         self.plan = mp_plan(cfg, len(devices))
         pl = self.plan.placement
@@ -293,6 +318,7 @@ class PipelineDistStrategy(Strategy):
 
     def __init__(self, cfg, model, device):
         super().__init__(cfg)
+        _refuse_optim_ext_mp(cfg)
         self.rank, self.local_rank, self.world = dist.get_rank(), dist_env()[1], dist.get_world_size()
         self.device = torch.device(device)
         self.model = model.to(self.device)
@@ -610,10 +636,15 @@ def train(cfg: TrainConfig):
                     curves.add_train(step, time.time() - t_start, mean_loss)
                     red = getattr(strat, "reducer", None)
                     comm_ms = red.exposed_comm_ms() if red is not None else None
+                    gn = {}
+                    if cfg.clip_grad_norm:        # the host has just waited for the losses: reading is free
+                        norm, coef = strat.optimizer.grad_norm()
+                        gn = dict(grad_norm=norm, clip_coef=coef)
                     metrics.log(kind="train", step=step, epoch=epoch, loss=mean_loss,
-                                lr=strat.optimizer.param_groups[0]["lr"], exposed_comm_ms=comm_ms)
+                                lr=strat.optimizer.param_groups[0]["lr"], exposed_comm_ms=comm_ms, **gn)
                     if strat.is_main:
-                        log.info(f"step {step} loss {mean_loss:.5f}")
+                        gtxt = f" gnorm {gn['grad_norm']:.4g}" if gn else ""
+                        log.info(f"step {step} loss {mean_loss:.5f}{gtxt}")
                     bar.set_postfix(loss=f"{mean_loss:.4f}")
                 stop_signal = _agree_stop(strat, guard.requested)
                 if stop_signal is not None:
@@ -636,15 +667,22 @@ def train(cfg: TrainConfig):
         val_loss, val_dice = evaluate(strat, val_loader, cfg)
         curves.add_val(step, time.time() - t_start, val_loss)
         plateau_step(scheduler, val_loss)
-        metrics.log(kind="epoch", epoch=epoch, step=step, val_loss=val_loss, val_dice=val_dice,
+        ema_val, ema_txt = {}, ""
+        if cfg.ema_decay:
+            # the same validation with the averaged parameters (the LR plateau keeps deciding on the live ones)
+            with strat.optimizer.swap_ema():
+                vl, vd = evaluate(strat, val_loader, cfg)
+            ema_val = dict(val_loss_ema=vl, val_dice_ema=vd)
+            ema_txt = f" ema: val_loss {vl:.5f} dice {vd:.4f}"
+        metrics.log(kind="epoch", epoch=epoch, step=step, val_loss=val_loss, val_dice=val_dice, **ema_val,
                     img_per_s=n_img * dp_ranks / max(ep_time, 1e-9),
                     img_per_s_steady=(None if steady_ips is None else steady_ips * dp_ranks),
                     peak_mem_gb=(torch.cuda.max_memory_allocated(strat.device) / 2 ** 30
                                  if strat.device.type == "cuda" else 0.0))
         if strat.is_main:
-            log.info(f"epoch {epoch}: val_loss {val_loss:.5f} val_dice {val_dice:.4f}")
+            log.info(f"epoch {epoch}: val_loss {val_loss:.5f} val_dice {val_dice:.4f}{ema_txt}")
             sps = "" if steady_ips is None else f", {steady_ips:.1f} img/s/rank after {steady.skip} warm-up steps"
-            print(f"epoch {epoch + 1}/{cfg.epochs} step {step} val_loss {val_loss:.5f} dice {val_dice:.4f} "
+            print(f"epoch {epoch + 1}/{cfg.epochs} step {step} val_loss {val_loss:.5f} dice {val_dice:.4f}{ema_txt} "
                   f"({n_img / max(ep_time, 1e-9):.1f} img/s/rank{sps})", flush=True)
         if cfg.save_every_epoch:
             sd_model, sd_opt = strat.state_dict(), strat.optimizer_state_dict()
@@ -667,6 +705,12 @@ def train(cfg: TrainConfig):
         ck = os.path.join(cfg.out_dir, "checkpoints", f"{cfg.train_method}.pth")
         save_model(_SD(sd), ck, module_prefix=strat.module_prefix)
         paths["checkpoint"] = ck
+        if cfg.ema_decay:
+            # the averaged parameters under the same keys (and the same module. prefix rule): evaluate.py and
+            # predict.py load it as -c <method>_ema
+            ck_ema = os.path.join(cfg.out_dir, "checkpoints", f"{cfg.train_method}_ema.pth")
+            save_model(_SD(strat.optimizer.ema_state_dict(strat.model)), ck_ema, module_prefix=strat.module_prefix)
+            paths["checkpoint_ema"] = ck_ema
     if strat.is_main:
         paths["loss"] = curves.save(cfg.out_dir, cfg.train_method)
     strat.barrier()
@@ -705,8 +749,10 @@ class GraphedStep:
         opt.enable_device_state()
         self.x = images.detach().clone()
         self.t = targets.detach().clone()
+        # (with --clip-grad-norm / --ema-decay: also the EMA buffers and the aux block the warm-up step wrote; the
+        # captured step then holds the norm and the extended Adam launches, nothing new is read on the host)
         snap = (space.data.clone(), [m.clone() for m in opt.exp_avg], [v.clone() for v in opt.exp_avg_sq],
-                opt.step_count)
+                opt.step_count, [e.clone() for e in opt.ema], [a.clone() for a in opt._aux])
         side = torch.cuda.Stream(strat.device)
         side.wait_stream(torch.cuda.current_stream(strat.device))
         with torch.cuda.stream(side):
@@ -729,6 +775,10 @@ class GraphedStep:
             m.copy_(s)
         for v, s in zip(opt.exp_avg_sq, snap[2]):
             v.copy_(s)
+        for e, s in zip(opt.ema, snap[4]):
+            e.copy_(s)
+        for a, s in zip(opt._aux, snap[5]):
+            a.copy_(s)
         opt.step_count = snap[3]
         opt.sync_device_state()
         space.touch()
