@@ -16,44 +16,71 @@ from ._lib import available as hip_available, check, ptr, stream_ptr
 c_float = ctypes.c_float
 c_ll = ctypes.c_longlong
 
+AUX_LEN = 8          # fp64 aux block: {sumsq, norm, coef, 1 - EMA decay of the step, reserved ...}
 
-def adam_step(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, bc1, bc2):
-    """In-place Adam (L2 decay) over flat fp32 tensors ``p, g, m, v`` (one launch)."""
+
+def _check_x(p, g, m, v, ema, aux):
+    ts = [p, g, m, v] + ([] if ema is None else [ema])
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() for t in ts)
+    assert aux is None or (aux.dtype == torch.float64 and aux.numel() >= AUX_LEN and aux.device == p.device)
+
+
+def _ptr_or_null(t):
+    return ctypes.c_void_p(None) if t is None else ptr(t)
+
+
+def adam_step(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, bc1, bc2, ema=None, aux=None, ema_decay=0.0):
+    """In-place Adam (L2 decay) over flat fp32 tensors ``p, g, m, v`` (one launch), with two options fused into
+    the same pass: ``aux`` given -> the gradient is used as ``aux[2] * g`` (the clip coefficient ``grad_sumsq``
+    left on the device; ``g`` itself is not changed); ``ema`` given -> ``ema += (1 - ema_decay) * (p_new - ema)``
+    on the just-updated parameter."""
     if not p.is_cuda:
         from ..optim import adam_reference
-        return adam_reference(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bc1, bc2)
-    assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32
-    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-    assert p.numel() == g.numel() == m.numel() == v.numel()
+        return adam_reference(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bc1, bc2,
+                              coef=None if aux is None else aux[2], ema=ema, ema_decay=ema_decay)
+    _check_x(p, g, m, v, ema, aux)
+    if p.numel() == 0:                       # (an empty tensor has no device pointer to hand over)
+        return
     L = _lib.lib()
-    err = L.dpa_adam_flat(ptr(p), ptr(g), ptr(m), ptr(v), c_ll(p.numel()), c_float(lr), c_float(beta1),
-                          c_float(beta2), c_float(eps), c_float(weight_decay), c_float(bc1), c_float(bc2),
+    err = L.dpa_adam_flat(ptr(p), ptr(g), ptr(m), ptr(v), _ptr_or_null(ema), c_ll(p.numel()), c_float(lr),
+                          c_float(beta1), c_float(beta2), c_float(eps), c_float(weight_decay), c_float(bc1),
+                          c_float(bc2), ctypes.c_double(ema_decay), _ptr_or_null(aux), ctypes.c_int(aux is not None),
                           ctypes.c_void_p(stream_ptr(p.device)))
     check(err, "adam_flat")
 
 
-def adam_step_dev(p, g, m, v, state, *, beta1, beta2, eps, weight_decay):
+def ema_decay_at(decay: float, step: int) -> float:
+    """EMA decay of optimizer step ``step`` (1-based): ``min(decay, (1 + step) / (10 + step))``."""
+    return min(float(decay), (1.0 + step) / (10.0 + step))
+
+
+def adam_step_dev(p, g, m, v, state, *, beta1, beta2, eps, weight_decay, aux=None, ema=None, clip=False,
+                  ema_decay=0.0):
     """Adam whose step count, lr and bias corrections live in ``state`` (fp64 device tensor
     ``[step, lr, 1/bc1, 1/sqrt(bc2)]``); the step increments ``state[0]`` itself, so one captured
-    launch sequence is valid for every replay of a HIP graph."""
+    launch sequence is valid for every replay of a HIP graph.  The options of ``adam_step``: ``clip`` scales the
+    gradient by ``aux[2]``; ``ema_decay`` is the ceiling D, the step's decay ``min(D, (1 + t) / (10 + t))`` is
+    computed on the device from the step count (``aux[3]``).  Either option needs ``aux``."""
     assert state.dtype == torch.float64 and state.numel() >= 4 and state.device == p.device
+    assert aux is not None or (not clip and ema is None)
     if not p.is_cuda:
         from ..optim import adam_reference
         t = float(state[0]) + 1.0
         state[0] = t
-        return adam_reference(p, g, m, v, float(state[1]), beta1, beta2, eps, weight_decay,
-                              1 - beta1 ** t, 1 - beta2 ** t)
-    assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32
-    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-    assert p.numel() == g.numel() == m.numel() == v.numel()
+        d = ema_decay_at(ema_decay, t)
+        if aux is not None:
+            aux[3] = 1.0 - d
+        return adam_reference(p, g, m, v, float(state[1]), beta1, beta2, eps, weight_decay, 1 - beta1 ** t,
+                              1 - beta2 ** t, coef=aux[2] if clip else None, ema=ema, ema_decay=d)
+    _check_x(p, g, m, v, ema, aux)
+    if p.numel() == 0:
+        return
     L = _lib.lib()
-    err = L.dpa_adam_flat_dev(ptr(p), ptr(g), ptr(m), ptr(v), c_ll(p.numel()), ptr(state), ctypes.c_double(beta1),
-                              ctypes.c_double(beta2), c_float(eps), c_float(weight_decay),
+    err = L.dpa_adam_flat_dev(ptr(p), ptr(g), ptr(m), ptr(v), _ptr_or_null(ema), c_ll(p.numel()), ptr(state),
+                              _ptr_or_null(aux), ctypes.c_double(beta1), ctypes.c_double(beta2), c_float(eps),
+                              c_float(weight_decay), ctypes.c_double(ema_decay), ctypes.c_int(bool(clip)),
                               ctypes.c_void_p(stream_ptr(p.device)))
     check(err, "adam_flat_dev")
-
-
-AUX_LEN = 8          # fp64 aux block: {sumsq, norm, coef, 1 - EMA decay of the step, reserved ...}
 
 
 def grad_sumsq_blocks(n: int) -> int:
@@ -85,62 +112,5 @@ def grad_sumsq(g, aux, max_norm, slab=None):
     check(err, "grad_sumsq")
 
 
-def _check_x(p, g, m, v, ema):
-    ts = [p, g, m, v] + ([] if ema is None else [ema])
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() for t in ts)
-
-
-def adam_step_x(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, bc1, bc2, ema=None, aux=None, ema_decay=0.0):
-    """``adam_step`` with two options fused into the same pass: ``aux`` given -> the gradient is used as
-    ``aux[2] * g`` (the clip coefficient ``grad_sumsq`` left on the device; ``g`` itself is not changed);
-    ``ema`` given -> ``ema += (1 - ema_decay) * (p_new - ema)`` on the just-updated parameter."""
-    if not p.is_cuda:
-        from ..optim import adam_x_reference
-        coef = None if aux is None else aux[2]
-        return adam_x_reference(p, g, m, v, lr, beta1, beta2, eps, weight_decay, bc1, bc2, coef=coef, ema=ema,
-                                ema_decay=ema_decay)
-    _check_x(p, g, m, v, ema)
-    if p.numel() == 0:
-        return
-    assert aux is None or (aux.dtype == torch.float64 and aux.numel() >= AUX_LEN and aux.device == p.device)
-    L = _lib.lib()
-    err = L.dpa_adam_flat_x(ptr(p), ptr(g), ptr(m), ptr(v), ctypes.c_void_p(None) if ema is None else ptr(ema),
-                            c_ll(p.numel()), c_float(lr), c_float(beta1), c_float(beta2), c_float(eps),
-                            c_float(weight_decay), c_float(bc1), c_float(bc2), ctypes.c_double(ema_decay),
-                            ctypes.c_void_p(None) if aux is None else ptr(aux), ctypes.c_int(aux is not None),
-                            ctypes.c_void_p(stream_ptr(p.device)))
-    check(err, "adam_flat_x")
-
-
-def ema_decay_at(decay: float, step: int) -> float:
-    """EMA decay of optimizer step ``step`` (1-based): ``min(decay, (1 + step) / (10 + step))``."""
-    return min(float(decay), (1.0 + step) / (10.0 + step))
-
-
-def adam_step_x_dev(p, g, m, v, state, aux, *, beta1, beta2, eps, weight_decay, ema=None, clip=False, ema_decay=0.0):
-    """``adam_step_dev`` with the options of ``adam_step_x``; ``ema_decay`` is the ceiling D, the step's decay
-    ``min(D, (1 + t) / (10 + t))`` is computed on the device from the step count in ``state`` (``aux[3]``)."""
-    assert state.dtype == torch.float64 and state.numel() >= 4 and state.device == p.device
-    assert aux.dtype == torch.float64 and aux.numel() >= AUX_LEN and aux.device == p.device
-    if not p.is_cuda:
-        from ..optim import adam_x_reference
-        t = float(state[0]) + 1.0
-        state[0] = t
-        d = ema_decay_at(ema_decay, t)
-        aux[3] = 1.0 - d
-        return adam_x_reference(p, g, m, v, float(state[1]), beta1, beta2, eps, weight_decay, 1 - beta1 ** t,
-                                1 - beta2 ** t, coef=aux[2] if clip else None, ema=ema, ema_decay=d)
-    _check_x(p, g, m, v, ema)
-    if p.numel() == 0:
-        return
-    L = _lib.lib()
-    err = L.dpa_adam_flat_x_dev(ptr(p), ptr(g), ptr(m), ptr(v), ctypes.c_void_p(None) if ema is None else ptr(ema),
-                                c_ll(p.numel()), ptr(state), ptr(aux), ctypes.c_double(beta1),
-                                ctypes.c_double(beta2), c_float(eps), c_float(weight_decay),
-                                ctypes.c_double(ema_decay), ctypes.c_int(bool(clip)),
-                                ctypes.c_void_p(stream_ptr(p.device)))
-    check(err, "adam_flat_x_dev")
-
-
-__all__ = ["adam_step", "adam_step_dev", "adam_step_x", "adam_step_x_dev", "grad_sumsq", "grad_sumsq_blocks",
+__all__ = ["adam_step", "adam_step_dev", "grad_sumsq", "grad_sumsq_blocks",
            "ema_decay_at", "AUX_LEN", "hip_available"]

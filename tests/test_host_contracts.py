@@ -55,6 +55,8 @@ def test_library_exports_and_version(L):
                  "dpa_up2_fwd", "dpa_up2_bwd", "dpa_adam_flat", "dpa_adam_flat_dev", "dpa_pack_weights",
                  "dpa_slab_fold", "dpa_loss_finish", "dpa_loss_grad"):
         assert hasattr(L, name), name
+    for suffix in ("_x", "_x_dev"):          # the one Adam kernel has two launchers, not four
+        assert not hasattr(L, "dpa_adam_flat" + suffix), suffix
     assert L.dpa_error_string(INVALID).decode() == "invalid argument"
 
 

@@ -1,6 +1,6 @@
 """Gradient-norm clipping and EMA weights in the fused optimizer step: definitions, optimizer state, trainer (CPU).
 
-The definitions (``optim.clip_coef_reference``, ``optim.adam_x_reference``) are checked against
+The definitions (``optim.clip_coef_reference``, ``optim.adam_reference``) are checked against
 ``torch.nn.utils.clip_grad_norm_`` + ``torch.optim.Adam`` + a hand-written EMA over several steps with different
 gradient norms: from zero moments Adam's first step does not depend on the gradient's scale, so one step could not
 tell whether the clip was applied.  The HIP kernels are checked against these definitions in
@@ -10,13 +10,15 @@ import dataclasses
 import json
 import logging
 import math
+import os
 
+import numpy as np
 import pytest
 import torch
 
 from distributedpytorch_amd.config import parse_args
 from distributedpytorch_amd.models.unet import build_model
-from distributedpytorch_amd.optim import (FlatParameterSpace, FusedAdam, adam_x_reference, clip_coef_reference)
+from distributedpytorch_amd.optim import FlatParameterSpace, FusedAdam, adam_reference, clip_coef_reference
 
 N = 1_000_003
 SCALES = (0.5, 4.0, 0.01, 2.0)          # norms of about 500, 4000, 10, 2000: steps 2 and 4 are clipped at C = 1000
@@ -25,6 +27,11 @@ C, WD, LR, D = 1000.0, 1e-8, 1e-3, 0.3  # D = 0.3: the schedule (1 + t) / (10 + 
 ARGS = ["--synthetic", "--synthetic-len", "16", "-v", "25", "--img-size", "32", "--model", "unet-tiny",
         "--backend", "torch", "--dtype", "fp32", "-b", "4", "--log-every", "1", "--lr", "1e-3"]
 EXT = ["--clip-grad-norm", "1e3", "--ema-decay", "0.99"]
+
+# tests/golden/adam_plain_bits.npz (tools/record_adam_bits.py): three steps of the default kernel on one gradient
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_plain_bits.npz")
+G_N, G_LR = 1027, 1e-3
+G_KW = dict(beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2)
 
 
 def _decay(t, d=D):
@@ -36,6 +43,40 @@ def _inputs():
     p0 = torch.randn(N, generator=gen)
     gs = [torch.randn(N, generator=gen) * s for s in SCALES]
     return p0, gs
+
+
+def _golden():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def test_golden_adam_bits_are_what_the_reference_computes():
+    """A corrupted or mis-recorded fixture would not land on the CPU definition (the tolerances of test_adam.py for
+    kernel against reference).
+
+    The launchers take the betas as C floats and the kernel forms 1 - beta in fp32, so the definition is given the
+    betas as the kernel sees them: float32(0.999) is 0.99900001, and 1 - 0.99900001 differs from 0.001 by 1.3e-5
+    relative, which is v's own error wherever (1 - b2) g^2 dominates it (|g| up to 1e2 here; with 0.999 as a Python
+    float v misses rtol 1e-5 at 103 of the 1027 elements, max 1.7e-5).  With the rounded betas the largest relative
+    errors are 3.8e-7 (p), 2.3e-6 (m) and 3.6e-7 (v).  The bias corrections stay 1 - 0.9 ** t and 1 - 0.999 ** t of
+    the Python floats: the recording formed them so on the host (fp64, from the unrounded betas) and handed them to
+    the launcher as numbers, and the device-state tick computes them in fp64 from double betas, so the kernel never
+    sees a bias correction made from a float32 beta."""
+    z = _golden()
+    assert sorted(z) == sorted(["p0", "g", "m0", "v0"] + [f"{f}_{n}" for f in ("host", "dev") for n in "pmv"])
+    for k, a in z.items():
+        assert a.dtype == np.float32 and a.shape == (G_N,) and np.isfinite(a).all(), k
+    assert (z["g"] == 0).sum() >= 3 and (z["v0"] == 0).sum() >= 3 and (z["v0"] >= 0).all()
+    mag = np.abs(z["g"][z["g"] != 0])
+    assert mag.min() < 1e-3 and mag.max() > 10.0                  # the gradient spans the magnitudes Adam sees
+    p, g, m, v = (torch.from_numpy(z[k].copy()) for k in ("p0", "g", "m0", "v0"))
+    b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))
+    for t in (1, 2, 3):
+        adam_reference(p, g, m, v, G_LR, b1, b2, 1e-8, G_KW["weight_decay"], 1 - 0.9 ** t, 1 - 0.999 ** t)
+    for form in ("host", "dev"):
+        for name, want in (("p", p), ("m", m), ("v", v)):
+            torch.testing.assert_close(torch.from_numpy(z[f"{form}_{name}"]), want, rtol=1e-5, atol=1e-6,
+                                       msg=lambda s, n=f"{form}_{name}": f"{n}: {s}")
 
 
 def _torch_trajectory(p0, gs, clip):
@@ -62,8 +103,8 @@ def test_references_match_torch_clip_adam_and_ema():
         sumsq, norm, coef = clip_coef_reference(g, C)
         assert norm == math.sqrt(sumsq)
         coefs.append(coef)
-        adam_x_reference(p, g, m, v, LR, 0.9, 0.999, 1e-8, WD, 1 - 0.9 ** t, 1 - 0.999 ** t, coef=coef, ema=e,
-                         ema_decay=_decay(t))
+        adam_reference(p, g, m, v, LR, 0.9, 0.999, 1e-8, WD, 1 - 0.9 ** t, 1 - 0.999 ** t, coef=coef, ema=e,
+                       ema_decay=_decay(t))
         assert torch.equal(g, g_before), "the gradient is scaled on the fly, not in place"
     assert coefs[0] == 1.0 and coefs[2] == 1.0 and coefs[1] < 0.3 and 0.4 < coefs[3] < 0.6, coefs
     torch.testing.assert_close(p, want_p, rtol=1e-5, atol=1e-6)

@@ -1,6 +1,6 @@
-"""csrc/optim_ext.hip on the GPU: the deterministic gradient norm, the Adam step with the clip coefficient and the
-EMA fused in, their launchers' argument checks, and the strategies that use them (singleGPU eager and graphed, DP,
-DDP over gloo on one device)."""
+"""The optimizer options of csrc/adam.hip on the GPU: the deterministic gradient norm, the Adam step with the clip
+coefficient and the EMA fused in, their launchers' argument checks, and the strategies that use them (singleGPU eager
+and graphed, DP, DDP over gloo on one device)."""
 import ctypes
 import os
 import socket
@@ -10,9 +10,9 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
-from distributedpytorch_amd.optim import adam_x_reference, clip_coef_reference
+from distributedpytorch_amd.optim import adam_reference, clip_coef_reference
 
-from test_optim_ext_cpu import C, D, LR, N, WD, _decay, _inputs  # noqa: E402
+from test_optim_ext_cpu import C, D, G_KW, G_LR, LR, N, WD, _decay, _golden, _inputs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -96,8 +96,8 @@ def _reference():
         p, m, v, e = p0.clone(), torch.zeros(N), torch.zeros(N), p0.clone()
         for t, g in enumerate(gs, 1):
             coef = clip_coef_reference(g, C)[2]
-            adam_x_reference(p, g, m, v, LR, 0.9, 0.999, 1e-8, WD, 1 - 0.9 ** t, 1 - 0.999 ** t, coef=coef, ema=e,
-                             ema_decay=_decay(t))
+            adam_reference(p, g, m, v, LR, 0.9, 0.999, 1e-8, WD, 1 - 0.9 ** t, 1 - 0.999 ** t, coef=coef, ema=e,
+                           ema_decay=_decay(t))
         _CACHE["ref"] = (p0, gs, p, m, v, e)
     return _CACHE["ref"]
 
@@ -117,10 +117,10 @@ def test_adam_x_host_and_device_state_match_the_reference(ops):
             g0 = g.clone()
             ops.grad_sumsq(g, aux, C, slab)
             if dev_state:
-                ops.adam_step_x_dev(p, g, m, v, state, aux, ema=e, clip=True, ema_decay=D, **kw)
+                ops.adam_step_dev(p, g, m, v, state, aux=aux, ema=e, clip=True, ema_decay=D, **kw)
             else:
-                ops.adam_step_x(p, g, m, v, lr=LR, bc1=1 - 0.9 ** t, bc2=1 - 0.999 ** t, ema=e, aux=aux,
-                                ema_decay=_decay(t), **kw)
+                ops.adam_step(p, g, m, v, lr=LR, bc1=1 - 0.9 ** t, bc2=1 - 0.999 ** t, ema=e, aux=aux,
+                              ema_decay=_decay(t), **kw)
             assert torch.equal(g, g0)                   # the gradient is scaled on the fly, not in place
         torch.cuda.synchronize()
         if dev_state:
@@ -132,27 +132,54 @@ def test_adam_x_host_and_device_state_match_the_reference(ops):
         torch.testing.assert_close(b, a, rtol=1e-6, atol=1e-7)
 
 
+MODES = ((False, False), (True, False), (False, True), (True, True))       # (coef == 1 from aux, EMA on)
+
+
+def _unit_coef_steps(ops, p0, g, m0, v0, steps, dev_state, coef, ema):
+    """``p, m, v`` after ``steps`` steps of the golden fixture's hyper-parameters on the same gradient, with the
+    options that must not change them: the clip coefficient read from aux where it is exactly 1, the EMA."""
+    p, m, v = p0.clone(), m0.clone(), v0.clone()
+    e = p0.clone() if ema else None
+    aux = _aux(ops) if coef or ema else None
+    if coef:
+        ops.grad_sumsq(g, aux, float("inf"))
+        assert float(aux[2]) == 1.0
+    state = torch.tensor([0.0, G_LR, 0.0, 0.0], dtype=torch.float64, device="cuda")
+    for k in range(1, steps + 1):
+        if dev_state:
+            ops.adam_step_dev(p, g, m, v, state, aux=aux, ema=e, clip=coef, ema_decay=D, **G_KW)
+        else:
+            ops.adam_step(p, g, m, v, lr=G_LR, bc1=1 - 0.9 ** k, bc2=1 - 0.999 ** k, aux=aux if coef else None,
+                          ema=e, ema_decay=_decay(k), **G_KW)
+    torch.cuda.synchronize()
+    if dev_state:
+        assert float(state[0]) == steps
+    if ema:
+        assert not torch.equal(e, p0)
+    return p, m, v
+
+
 def test_adam_x_with_unit_coef_is_bitwise_the_plain_kernel(ops):
+    """The plain kernel is the one recorded in tests/golden/adam_plain_bits.npz (tools/record_adam_bits.py, from the
+    tree that still had a separate plain kernel): with no options, with coef == 1 read from aux, with the EMA and
+    with both, the host-state and the device-state form give those bits after three steps.  Then the modes against
+    each other on a million elements (more than one block per CU, a tail of 3)."""
+    z = _golden()
+    inputs = [torch.from_numpy(z[k]).cuda() for k in ("p0", "g", "m0", "v0")]
+    for dev_state in (False, True):
+        form = "dev" if dev_state else "host"
+        for coef, ema in MODES:
+            got = _unit_coef_steps(ops, *inputs, 3, dev_state, coef, ema)
+            for name, t in zip("pmv", got):
+                assert torch.equal(t.cpu(), torch.from_numpy(z[f"{form}_{name}"])), (form, coef, ema, name)
     torch.manual_seed(0)
     p0, g = torch.randn(N, device="cuda"), torch.randn(N, device="cuda")
     m0, v0 = torch.randn(N, device="cuda").abs() * 0.1, torch.randn(N, device="cuda").abs() * 0.1
-    aux = _aux(ops)
-    ops.grad_sumsq(g, aux, float("inf"))
-    assert float(aux[2]) == 1.0
-    outs = []
-    for mode in ("plain", "coef", "neither"):
-        p, m, v = p0.clone(), m0.clone(), v0.clone()
-        for k in (1, 2):
-            kw = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, bc1=1 - 0.9 ** k,
-                      bc2=1 - 0.999 ** k)
-            if mode == "plain":
-                ops.adam_step(p, g, m, v, **kw)
-            else:
-                ops.adam_step_x(p, g, m, v, aux=aux if mode == "coef" else None, **kw)
-        outs.append((p, m, v))
-    for other in outs[1:]:
-        for a, b in zip(outs[0], other):
-            assert torch.equal(a, b)
+    for dev_state in (False, True):
+        outs = [_unit_coef_steps(ops, p0, g, m0, v0, 2, dev_state, coef, ema) for coef, ema in MODES]
+        for other in outs[1:]:
+            for a, b in zip(outs[0], other):
+                assert torch.equal(a, b)
 
 
 def test_adam_x_zero_lr_keeps_p_and_halves_the_distance_to_ema(ops):
@@ -162,8 +189,8 @@ def test_adam_x_zero_lr_keeps_p_and_halves_the_distance_to_ema(ops):
     e0 = torch.randint(-50, 51, (n,), generator=gen).float().cuda()
     g = torch.randn(n, generator=gen).cuda()
     p, e, m, v = p0.clone(), e0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
-    ops.adam_step_x(p, g, m, v, lr=0.0, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-8, bc1=0.1, bc2=0.001,
-                    ema=e, ema_decay=0.5)
+    ops.adam_step(p, g, m, v, lr=0.0, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-8, bc1=0.1, bc2=0.001,
+                  ema=e, ema_decay=0.5)
     assert torch.equal(p, p0)
     assert torch.equal(e, (p0 + e0) / 2)
     assert float(m.abs().max()) > 0
@@ -183,11 +210,11 @@ def test_launchers_refuse_bad_arguments(ops, hip_lib):
         a = dict(p=p, g=g, ema=e)
         a.update(bad)
         with pytest.raises(RuntimeError, match="invalid"):
-            ops.adam_step_x(a["p"], a["g"], m, v, ema=a["ema"], ema_decay=0.5, **kw)
+            ops.adam_step(a["p"], a["g"], m, v, ema=a["ema"], ema_decay=0.5, **kw)
         state = torch.tensor([0.0, 1e-3, 0.0, 0.0], dtype=torch.float64, device="cuda")
         with pytest.raises(RuntimeError, match="invalid"):
-            ops.adam_step_x_dev(a["p"], a["g"], m, v, state, aux, ema=a["ema"], ema_decay=0.5, beta1=0.9, beta2=0.999,
-                                eps=1e-8, weight_decay=0.0)
+            ops.adam_step_dev(a["p"], a["g"], m, v, state, aux=aux, ema=a["ema"], ema_decay=0.5, beta1=0.9,
+                              beta2=0.999, eps=1e-8, weight_decay=0.0)
         assert float(state[0]) == 0.0                    # refused before the tick
     assert ops.grad_sumsq_blocks(n) == 4
     with pytest.raises(RuntimeError, match="invalid"):
@@ -203,9 +230,9 @@ def test_launchers_refuse_bad_arguments(ops, hip_lib):
         return L.dpa_grad_sumsq(vp(gp), ll(nn), vp(sp), ll(4), vp(ap), one, vp(0))
 
     def adam(pp, nn, auxp, clip):
-        return L.dpa_adam_flat_x(vp(pp), vp(g.data_ptr()), vp(m.data_ptr()), vp(v.data_ptr()), vp(None), ll(nn),
-                                 f(1e-3), f(0.9), f(0.999), f(1e-8), f(0.0), f(0.1), f(0.001), ctypes.c_double(0.0),
-                                 vp(auxp), ctypes.c_int(clip), vp(0))
+        return L.dpa_adam_flat(vp(pp), vp(g.data_ptr()), vp(m.data_ptr()), vp(v.data_ptr()), vp(None), ll(nn),
+                               f(1e-3), f(0.9), f(0.999), f(1e-8), f(0.0), f(0.1), f(0.001), ctypes.c_double(0.0),
+                               vp(auxp), ctypes.c_int(clip), vp(0))
 
     assert sumsq(g.data_ptr(), -1, slab.data_ptr(), aux.data_ptr()) == INVALID
     assert sumsq(None, n, slab.data_ptr(), aux.data_ptr()) == INVALID
@@ -216,7 +243,24 @@ def test_launchers_refuse_bad_arguments(ops, hip_lib):
     assert adam(None, n, None, 0) == INVALID
     assert adam(p.data_ptr(), n, None, 1) == INVALID     # clipping needs the aux block
     assert adam(p.data_ptr(), 0, None, 0) == 0
+    assert adam(off.data_ptr(), n, None, 0) == INVALID   # the default step (no EMA, no aux, no clip) is checked too
+    state = torch.tensor([0.0, 1e-3, 0.0, 0.0], dtype=torch.float64, device="cuda")
+
+    def adam_dev(pp, nn, auxp, clip):
+        return L.dpa_adam_flat_dev(vp(pp), vp(g.data_ptr()), vp(m.data_ptr()), vp(v.data_ptr()), vp(None), ll(nn),
+                                   vp(state.data_ptr()), vp(auxp), ctypes.c_double(0.9), ctypes.c_double(0.999),
+                                   f(1e-8), f(0.0), ctypes.c_double(0.0), ctypes.c_int(clip), vp(0))
+
+    assert adam_dev(p.data_ptr(), -1, None, 0) == INVALID
+    assert adam_dev(None, n, None, 0) == INVALID
+    assert adam_dev(off.data_ptr(), n, None, 0) == INVALID
+    assert adam_dev(p.data_ptr(), 0, None, 0) == 0
+    assert adam_dev(p.data_ptr(), n, None, 1) == INVALID             # clipping needs the aux block
     torch.cuda.synchronize()
+    assert float(state[0]) == 0.0                                    # refused (or n == 0) before the tick
+    assert adam_dev(p.data_ptr(), n, None, 0) == 0                   # no clip, no EMA: no aux block needed
+    torch.cuda.synchronize()
+    assert float(state[0]) == 1.0
     assert torch.equal(aux.cpu(), torch.full((ops.AUX_LEN,), 5.0, dtype=torch.float64))    # nothing was launched
     assert float(p.abs().max()) == 0.0
 

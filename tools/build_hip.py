@@ -23,9 +23,10 @@ ARCH = os.environ.get("DPA_ARCH", "gfx950")
 # Per-file flags, after the common ones.  predict_post.hip reproduces PIL's double sums (a rounded multiply, then
 # a rounded add) and says so with `#pragma clang fp contract(off)`; plain `-ffp-contract=fast` lets the backend
 # fuse them into an fma all the same.
-# optim_ext.hip turns contraction off where its Adam must round exactly as adam.hip's object code does.
+# adam.hip turns contraction off in the Adam update and spells its fmas out, so that every instantiation of the
+# kernel (clip, EMA, host or device state) rounds alike.
 FILE_FLAGS = {"predict_post.hip": ["-ffp-contract=fast-honor-pragmas"],
-              "optim_ext.hip": ["-ffp-contract=fast-honor-pragmas"]}
+              "adam.hip": ["-ffp-contract=fast-honor-pragmas"]}
 
 
 def torch_lib_dir() -> Path:
