@@ -64,7 +64,8 @@ def _declare(L):
                  "dpa_prob_to_mask_u8", "dpa_mask_rle", "dpa_mask_rle_tiles",
                  "dpa_prob_score", "dpa_prob_score_blocks",
                  "dpa_mask_clean", "dpa_mask_clean_work", "dpa_mask_score", "dpa_mask_score_blocks",
-                 "dpa_grad_sumsq", "dpa_grad_sumsq_blocks"):
+                 "dpa_grad_sumsq", "dpa_grad_sumsq_blocks",
+                 "dpa_tta_views_f32", "dpa_tta_accum"):
         getattr(L, name).restype = ctypes.c_int
     L.dpa_head_slab_blocks.restype = ctypes.c_int
     L.dpa_head_slab_blocks.argtypes = [ctypes.c_longlong]

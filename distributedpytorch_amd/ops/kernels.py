@@ -2081,3 +2081,101 @@ def mask_score(masks: torch.Tensor, truth: torch.Tensor, cut: torch.Tensor):
     _check(L.dpa_mask_score(_p(masks), _p(truth), _p(cut), c_int(B), c_int(H), c_int(W), _p(counts), _p(work),
                             c_ll(work.numel()), _stream(masks)), "mask_score")
     return counts
+
+
+# ---- test-time augmentation and ensembling (csrc/tta.hip): mirrored views in, averaged probabilities out ------
+TTA_NAMES = ("hflip", "vflip", "hvflip")             # canonical order; code bit 0 mirrors x (width), bit 1 y (height)
+TTA_VMAX = 4                                         # views one dpa_tta_views_f32 launch writes
+
+
+def parse_tta(spec) -> str:
+    """``--tta``: ``none``, or names from ``hflip``, ``vflip`` and ``hvflip`` joined by ``+`` in any order -> the
+    canonical string (``hvflip+hflip`` -> ``hflip+hvflip``).  Raises ``ValueError`` naming an unknown or empty
+    part."""
+    parts = [t.strip() for t in str(spec).split("+")]
+    if parts == ["none"]:
+        return "none"
+    for t in parts:
+        if t not in TTA_NAMES:
+            what = "an empty part" if not t else f"unknown part {t!r}"
+            raise ValueError(f"tta spec {str(spec)!r} has {what}: use none, or names from hflip, vflip and hvflip "
+                             f"joined by +")
+    return "+".join(n for n in TTA_NAMES if n in parts)
+
+
+def tta_codes(spec) -> list:
+    """The mirror codes of the views of a ``--tta`` spec, the identity first: ``none`` -> ``[0]``,
+    ``hflip+hvflip`` -> ``[0, 1, 3]``."""
+    names = parse_tta(spec).split("+")
+    return [0] + [i + 1 for i, n in enumerate(TTA_NAMES) if n in names]
+
+
+def _mirror(a, code: int):
+    """The last two axes of ``a`` mirrored by ``code`` (bit 0: the last axis, bit 1: the one before it)."""
+    assert 0 <= int(code) <= 3, f"mirror code {code}: 0 to 3"
+    if code & 1:
+        a = a[..., ::-1]
+    if code & 2:
+        a = a[..., ::-1, :]
+    return a
+
+
+def tta_views_reference(u8, codes):
+    """The definition of the views, in numpy: uint8 ``[B, C, h, w]`` -> float32 ``[V, B, C, h, w]``, view ``v`` =
+    ``float32(byte / 255.0)`` (``unit_table``) mirrored by ``codes[v]``."""
+    import numpy as np
+    u8 = np.asarray(u8)
+    assert u8.dtype == np.uint8 and u8.ndim == 4
+    unit = (np.arange(256, dtype=np.float64) / 255.0).astype(np.float32)
+    x = unit[u8]
+    return np.stack([np.ascontiguousarray(_mirror(x, int(c))) for c in codes])
+
+
+def tta_merge_reference(members, codes):
+    """The definition of the merge, in numpy.  ``members``: N arrays ``[B, h, w]`` (float32, or bfloat16 values
+    held in float32), member k computed from a view mirrored by ``codes[k]``; checkpoint-major: the checkpoints in
+    the order given, per checkpoint the views in canonical order.  ``q_k`` = float32(member k) mirrored back;
+    ``acc_0 = q_0``, ``acc_k = float32(acc_{k-1} + q_k)`` in member order; the result is ``float32(acc_{N-1} * r)``
+    with ``r = float32(1.0 / N)`` (a float64 division, rounded)."""
+    import numpy as np
+    assert len(members) == len(codes) >= 1, f"tta_merge: {len(members)} members, {len(codes)} codes"
+    acc = None
+    for m, c in zip(members, codes):
+        q = _mirror(np.asarray(m).astype(np.float32), int(c))
+        assert q.ndim == 3 and (acc is None or q.shape == acc.shape)
+        acc = q.copy() if acc is None else (acc + q).astype(np.float32)
+    return (acc * np.float32(1.0 / len(members))).astype(np.float32)
+
+
+def tta_views(u8: torch.Tensor, codes) -> torch.Tensor:
+    """``tta_views_reference`` on the device: ``u8`` uint8 ``[B, C, h, w]`` and 1 to 4 mirror codes -> float32
+    ``[V, B, C, h, w]``, all views from one launch."""
+    _u8(u8, "tta_views.u8")
+    codes = [int(c) for c in codes]
+    V = len(codes)
+    assert u8.dim() == 4 and min(u8.shape) > 0, f"tta_views: need [B, C, h, w], got {tuple(u8.shape)}"
+    assert 1 <= V <= TTA_VMAX and all(0 <= c <= 3 for c in codes), f"tta_views: 1 to {TTA_VMAX} codes in 0..3, got {codes}"
+    B, C, h, w = u8.shape
+    assert u8.numel() < 2 ** 31, f"tta_views: {tuple(u8.shape)} is beyond the launcher's limits"
+    dst = torch.empty(V, B, C, h, w, dtype=torch.float32, device=u8.device)
+    host_codes = (c_int * V)(*codes)                  # read by the launcher before it returns
+    _check(_lib.lib().dpa_tta_views_f32(_p(u8), c_int(B), c_int(C), c_int(h), c_int(w), _p(unit_table(u8.device)),
+                                        host_codes, c_int(V), _p(dst), _stream(u8)), "tta_views")
+    return dst
+
+
+def tta_accum(acc: torch.Tensor, src: torch.Tensor, code: int, first: bool, last: bool, scale: float = 1.0) -> None:
+    """One member of ``tta_merge_reference`` on the device: ``acc`` float32 ``[B, h, w]`` = (``first``: nothing,
+    else ``acc``) + ``src`` mirrored back by ``code``, times ``float32(scale)`` when ``last``.  ``src`` is bfloat16
+    or float32, ``[B, h, w]`` or ``[B, 1, h, w]``.  Launch the members in order on one stream."""
+    assert acc.dtype == torch.float32 and acc.is_cuda and acc.is_contiguous() and acc.dim() == 3, \
+        f"tta_accum.acc: need a contiguous cuda float32 [B, h, w] tensor, got {acc.dtype} {tuple(acc.shape)} on {acc.device}"
+    assert src.dtype in (torch.bfloat16, torch.float32) and src.is_contiguous() and src.device == acc.device, \
+        f"tta_accum.src: need a contiguous bfloat16 or float32 tensor on {acc.device}, got {src.dtype} on {src.device}"
+    B, h, w = acc.shape
+    assert tuple(src.shape) in ((B, h, w), (B, 1, h, w)), f"tta_accum: src {tuple(src.shape)} for acc {tuple(acc.shape)}"
+    assert min(B, h, w) > 0 and acc.numel() < 2 ** 31 and 0 <= int(code) <= 3, f"tta_accum: code {code}, acc {tuple(acc.shape)}"
+    assert src.data_ptr() != acc.data_ptr(), "tta_accum: src and acc must not overlap"
+    _check(_lib.lib().dpa_tta_accum(_p(src), c_int(int(src.dtype == torch.bfloat16)), c_int(int(code)), c_int(B),
+                                    c_int(h), c_int(w), _p(acc), c_int(int(bool(first))), c_int(int(bool(last))),
+                                    ctypes.c_float(float(scale)), _stream(acc)), "tta_accum")

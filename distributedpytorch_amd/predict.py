@@ -33,6 +33,13 @@ run lengths: the largest 8-connected component, then the holes of what is kept f
 the requested masks come back; scoring then goes mask -> clean -> ``dpa_mask_score`` per threshold, since a cleaned
 mask cannot be counted in registers straight from the probabilities.  ``ops.kernels.clean_reference`` (numpy) defines
 the result and is the host path.  With ``none`` nothing of this runs.
+
+``tta`` (``--tta``: ``hflip``, ``vflip``, ``hvflip`` joined by ``+``) and ``extra_models`` (``--ensemble``) average
+the probabilities of the mirrored views and of several checkpoints before any of the above sees them
+(:meth:`Predictor.merged_probs`): one forward of the batch per view and checkpoint, ``dpa_tta_views_f32`` (all views
+from the resized bytes in one launch) in front and one ``dpa_tta_accum`` behind each (csrc/tta.hip).
+``ops.kernels.tta_merge_reference`` (numpy) defines the average and is the host path.  Without either, nothing of
+this runs.
 """
 from __future__ import annotations
 
@@ -72,21 +79,35 @@ class Predictor:
     ``host_post`` forces the host post-processing; ``rle_cap`` is the capacity of one device run list (default
     ``4 * source height``; a list that overflows it is finished on the host); ``clean`` is a ``--clean`` spec
     (``ops.kernels.parse_clean``): masks, run lists and scores are then those of the cleaned masks, and
-    ``clean_stats`` sums (components before cleaning, pixels removed, pixels filled) over the files."""
+    ``clean_stats`` sums (components before cleaning, pixels removed, pixels filled) over the files; ``tta`` is a
+    ``--tta`` spec (``ops.kernels.parse_tta``) and ``extra_models`` further models of the same ``in_channels``
+    (``ValueError`` otherwise): the probabilities are then the average over the views and the models."""
 
     def __init__(self, model, device, img_size, dtype: Optional[str] = None, backend: str = "auto",
                  threshold: float = 0.5, host_post: bool = False, rle_cap: Optional[int] = None,
-                 clean: str = "none"):
+                 clean: str = "none", tta: str = "none", extra_models: Sequence = ()):
         from .config import TrainConfig
+        from .ops.kernels import parse_tta, tta_codes
         from .trainer import SingleDevice
         self.device = torch.device(device)
         self.on_gpu = self.device.type == "cuda"
         self.h, self.w = int(img_size[0]), int(img_size[-1])
         self.dtype = dtype or ("bf16" if self.on_gpu else "fp32")
+        self.channels = int(model.cfg.in_channels)
+        self.tta = parse_tta(tta)
+        self.tta_codes = tta_codes(self.tta)
+        extra_models = list(extra_models)
+        for k, m in enumerate(extra_models):
+            if int(m.cfg.in_channels) != self.channels:
+                raise ValueError(f"extra_models[{k}] takes {int(m.cfg.in_channels)} input channels, the first model "
+                                 f"{self.channels}")
         cfg = TrainConfig(backend=backend, img_size=(self.h, self.w), dtype=self.dtype)
         self.strat = SingleDevice(cfg, model, self.device)
         self.strat.set_train(False)
-        self.channels = int(model.cfg.in_channels)
+        self.strats = [self.strat]          # the ensemble, first member first
+        for m in extra_models:
+            self.strats.append(SingleDevice(cfg, m, self.device))
+            self.strats[-1].set_train(False)
         self.threshold = float(threshold)
         self.host_post = bool(host_post) or not self.on_gpu
         self.rle_cap = None if rle_cap is None else int(rle_cap)
@@ -117,23 +138,33 @@ class Predictor:
         return BasicDataset.preprocess(pil_img, (self.w, self.h), is_mask=False).astype(np.float32)
 
     # ---- one batch ----------------------------------------------------------------------------------------
-    def _inputs(self, items) -> torch.Tensor:
-        """float32 ``[B, C, h, w]`` on the device: the training preprocessing of the decoded files."""
+    def _resize_raw(self, items):
+        """The device resize of the full-size sources among ``items``: (uint8 ``[R, C, h, w]``, [(row, item)] of
+        the items it resized), or (None, []) when there is none.  An item the kernel refuses becomes a CPU item."""
+        raw = [i for i, (_, _, r) in enumerate(items) if r]
+        if not raw:
+            return None, []
+        from .ops import kernels as K
+        u8 = torch.empty(len(raw), self.channels, self.h, self.w, dtype=torch.uint8, device=self.device)
+        kept = []
+        for j, i in enumerate(raw):
+            arr = items[i][1]
+            if K.resize_bicubic_u8(torch.from_numpy(arr).to(self.device, non_blocking=True), u8[j]):
+                kept.append((j, i))
+            else:                       # extreme down-scaling: PIL on the CPU, as DeviceFolderDataset does
+                from PIL import Image
+                pil = Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr)
+                items[i] = (items[i][0], self._cpu_image(pil), False)
+        return u8, kept
+
+    def _inputs(self, items, resized=None) -> torch.Tensor:
+        """float32 ``[B, C, h, w]`` on the device: the training preprocessing of the decoded files.  ``resized``:
+        what ``_resize_raw(items)`` returned, when the caller ran it already."""
         B = len(items)
         x = torch.empty(B, self.channels, self.h, self.w, dtype=torch.float32, device=self.device)
-        raw = [i for i, (_, _, r) in enumerate(items) if r]
-        if raw:
+        u8, kept = self._resize_raw(items) if resized is None else resized
+        if u8 is not None:
             from .ops import kernels as K
-            u8 = torch.empty(len(raw), self.channels, self.h, self.w, dtype=torch.uint8, device=self.device)
-            kept = []
-            for j, i in enumerate(raw):
-                arr = items[i][1]
-                if K.resize_bicubic_u8(torch.from_numpy(arr).to(self.device, non_blocking=True), u8[j]):
-                    kept.append((j, i))
-                else:                       # extreme down-scaling: PIL on the CPU, as DeviceFolderDataset does
-                    from PIL import Image
-                    pil = Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr)
-                    items[i] = (items[i][0], self._cpu_image(pil), False)
             if kept:
                 js = torch.tensor([j for j, _ in kept], device=self.device)
                 dst = torch.tensor([i for _, i in kept], device=self.device)
@@ -149,6 +180,52 @@ class Predictor:
         p = self.strat.compute.probs(x)
         assert p.dim() == 4 and p.shape[1] == 1, f"probs: expected [B, 1, h, w], got {tuple(p.shape)}"
         return p.to(torch.float32).reshape(p.shape[0], p.shape[2], p.shape[3]).contiguous()
+
+    @property
+    def members(self) -> int:
+        """Forward passes averaged per image: views x checkpoints."""
+        return len(self.tta_codes) * len(self.strats)
+
+    @torch.no_grad()
+    def merged_probs(self, items) -> torch.Tensor:
+        """float32 ``[B, h, w]`` probabilities of a decoded batch: the average over the mirrored views (``tta``) and
+        the checkpoints (``extra_models``) as ``ops.kernels.tta_merge_reference`` defines it, members
+        checkpoint-major; one forward of the B images per member, the views built once and shared by the
+        checkpoints.  With one member this is ``probs(_inputs(items))`` and nothing else.  On a GPU
+        ``dpa_tta_views_f32`` makes the views from the resized bytes and ``dpa_tta_accum`` adds each member up
+        behind its forward; the host path (``host_post``, a CPU device) flips with torch and merges with numpy."""
+        if self.members == 1:
+            return self.probs(self._inputs(items))
+        from .ops import kernels as K
+        codes, B = self.tta_codes, len(items)
+        views = None
+        if not self.host_post:
+            u8, kept = resized = self._resize_raw(items)
+            if len(kept) == B:              # every file took the device resize: row j of u8 is item j
+                views = K.tta_views(u8, codes)
+        else:
+            resized = None
+        if views is None:
+            x = self._inputs(items, resized)
+            views = [x if c == 0 else torch.flip(x, [d for d, bit in ((3, 1), (2, 2)) if c & bit]) for c in codes]
+        N = self.members
+        scale = float(np.float32(1.0 / N))
+        acc = None if self.host_post else torch.empty(B, self.h, self.w, dtype=torch.float32, device=self.device)
+        got, k = [], 0
+        for strat in self.strats:
+            for v, c in enumerate(codes):
+                p = strat.compute.probs(views[v])
+                assert p.dim() == 4 and p.shape[1] == 1, f"probs: expected [B, 1, h, w], got {tuple(p.shape)}"
+                if self.host_post:
+                    got.append(p.to(torch.float32).reshape(B, self.h, self.w).cpu().numpy())
+                else:
+                    if p.dtype not in (torch.bfloat16, torch.float32):
+                        p = p.to(torch.float32)
+                    K.tta_accum(acc, p.contiguous(), c, k == 0, k == N - 1, scale)
+                k += 1
+        if self.host_post:
+            return torch.from_numpy(K.tta_merge_reference(got, codes * len(self.strats))).to(self.device)
+        return acc
 
     def _add_clean_stats(self, stats) -> None:
         stats = np.asarray(stats, np.int64).reshape(-1, 3)
@@ -365,7 +442,7 @@ class Predictor:
         order.  ``workers``: decode threads; 0 means ``min(8, os.cpu_count())``; never more than 16."""
         for chunk, items in self._batches(paths, self._decode, batch_size, workers):
             sizes = [s for s, _, _ in items]
-            res = self.post(self.probs(self._inputs(items)), sizes, want_masks, want_rle)
+            res = self.post(self.merged_probs(items), sizes, want_masks, want_rle)
             for p, s, (m, r) in zip(chunk, sizes, res):
                 yield p, s, m, r
 
@@ -377,7 +454,7 @@ class Predictor:
         post = want_masks or want_rle
         for chunk, items in self._batches(pairs, self._decode_pair, batch_size, workers):
             sizes = [it[0] for it in items]
-            probs = self.probs(self._inputs([it[:3] for it in items]))
+            probs = self.merged_probs([it[:3] for it in items])
             res = self.post(probs, sizes, want_masks, want_rle) if post else [(None, None)] * len(items)
             counts = self.score(probs, [it[3] for it in items], [it[4] for it in items], thresholds,
                                 count_host=not post)
@@ -450,6 +527,23 @@ def _clean_spec(text: str) -> str:
         raise argparse.ArgumentTypeError(str(e))
 
 
+def _tta_spec(text: str) -> str:
+    """``--tta``: the canonical spec string (``vflip+hflip`` -> ``hflip+vflip``)."""
+    from .ops.kernels import parse_tta
+    try:
+        return parse_tta(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def ensemble_path(entry: str, out_dir: str) -> str:
+    """``--ensemble``: an entry without a path separator and without a ``.pth`` ending names
+    ``<out_dir>/checkpoints/<entry>.pth``; anything else is a path."""
+    if os.sep in entry or (os.altsep and os.altsep in entry) or entry.endswith(".pth"):
+        return entry
+    return os.path.join(out_dir, "checkpoints", f"{entry}.pth")
+
+
 def rle_string(runs) -> str:
     return " ".join(str(int(v)) for v in np.asarray(runs).reshape(-1))
 
@@ -474,6 +568,13 @@ def main(argv=None):
                     help="clean every mask after the threshold: none, or largest (keep the largest 8-connected "
                          "component) and fill (fill enclosed holes) joined by +; masks, run lists and scores are "
                          "those of the cleaned masks")
+    ap.add_argument("--tta", type=_tta_spec, default="none", metavar="SPEC",
+                    help="average the probabilities over mirrored views: none, or hflip, vflip and hvflip joined by "
+                         "+ (the image itself always counts); one forward per view")
+    ap.add_argument("--ensemble", nargs="+", default=[], metavar="CKPT",
+                    help="further checkpoints of the same --model whose probabilities are averaged with the first "
+                         "(-c / -l): NAME means <out-dir>/checkpoints/NAME.pth, anything with a path separator or "
+                         "ending in .pth is a path")
     ap.add_argument("--out-dir", default=".", help="where checkpoints/ lives")
     ap.add_argument("--model", default="unet")
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"])
@@ -499,6 +600,10 @@ def main(argv=None):
         ap.error("no checkpoint: give -c NAME or -l PATH")
     if not os.path.isfile(path):
         ap.error(f"checkpoint not found: {path}")
+    more = [ensemble_path(e, a.out_dir) for e in a.ensemble]
+    for p in more:
+        if not os.path.isfile(p):
+            ap.error(f"--ensemble: checkpoint not found: {p}")
     files = list_inputs(a.input)
     if not files:
         ap.error(f"no input file found in {' '.join(a.input)}")
@@ -516,9 +621,13 @@ def main(argv=None):
 
     model = build_model(a.model)
     load_model_state(model, path)
+    extra = []
+    for p in more:
+        extra.append(build_model(a.model))
+        load_model_state(extra[-1], p)
     dev = "cuda:0" if torch.cuda.is_available() else "cpu"
     pred = Predictor(model, dev, (a.img_size[0], a.img_size[-1]), dtype=a.dtype, backend=a.backend,
-                     threshold=a.threshold, host_post=a.host_post, clean=a.clean)
+                     threshold=a.threshold, host_post=a.host_post, clean=a.clean, tta=a.tta, extra_models=extra)
     if a.output:
         os.makedirs(a.output, exist_ok=True)
     rows, scored = [], []
@@ -547,6 +656,8 @@ def main(argv=None):
     print(f"predicted {len(files)} files in {dt:.2f} s: {len(files) / dt:.1f} img/s, {pred.host_finished} finished on "
           f"the host (backend {pred.strat.compute.name}, dtype {pred.dtype}, post-processing "
           f"{'host' if pred.host_post else 'device'})")
+    if pred.members > 1:
+        print(f"merged (tta {pred.tta}): {len(pred.tta_codes)} views x {len(pred.strats)} checkpoints")
     if pred.clean != "none":
         print(f"cleaned ({pred.clean}): {pred.clean_removed} components removed "
               f"from {pred.clean_files} files, {int(pred.clean_stats[2])} pixels filled")

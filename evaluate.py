@@ -67,9 +67,15 @@ def main(argv=None):
     ap.add_argument("--clean", type=_clean_spec, default="none", metavar="SPEC",
                     help="clean the masks of --full-res before scoring (as predict.py --clean): none, or largest "
                          "and fill joined by +")
+    from distributedpytorch_amd.predict import _tta_spec
+    ap.add_argument("--tta", type=_tta_spec, default="none", metavar="SPEC",
+                    help="average the probabilities of --full-res over mirrored views (as predict.py --tta): none, "
+                         "or hflip, vflip and hvflip joined by +")
     a = ap.parse_args(argv)
     if a.clean != "none" and not a.full_res:
         ap.error(f"--clean {a.clean} needs --full-res: only the full-size masks are cleaned")
+    if a.tta != "none" and not a.full_res:
+        ap.error(f"--tta {a.tta} needs --full-res: only the full-size scoring averages over views")
     if a.full_res and a.synthetic:
         ap.error("--full-res scores image files: give a --data-dir, not --synthetic")
     H, W = (a.img_size[0], a.img_size[-1])
@@ -111,12 +117,13 @@ def main(argv=None):
     ds = CarvanaDataset(os.path.join(a.data_dir, "train_hq"), os.path.join(a.data_dir, "train_masks"), newsize=(W, H))
     _, held_out = split_dataset(ds, a.validation, seed=0)
     pairs = [tuple(str(p) for p in ds._pairs[i]) for i in held_out.indices]
-    pred = Predictor(model, dev, (H, W), dtype=dtype, backend=a.backend, threshold=a.threshold, clean=a.clean)
+    pred = Predictor(model, dev, (H, W), dtype=dtype, backend=a.backend, threshold=a.threshold, clean=a.clean,
+                     tta=a.tta)
     counts = np.stack([c for _, _, c in pred.score_files(pairs, a.batch_size)]) if pairs else np.zeros((0, 3), np.int64)
     d, i = dice_iou(counts)
     full = (float(d.mean()), float(i.mean())) if len(pairs) else (float("nan"), float("nan"))
     print(f"full_res dice {full[0]:.6f} iou {full[1]:.6f} ({len(pairs)} images, threshold {a.threshold:g}"
-          f"{'' if a.clean == 'none' else ', clean ' + a.clean})")
+          f"{'' if a.clean == 'none' else ', clean ' + a.clean}{'' if a.tta == 'none' else ', tta ' + a.tta})")
     return loss, dice, full
 
 
