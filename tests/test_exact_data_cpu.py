@@ -5,13 +5,16 @@ test_exact_fp32.py) goes through the generators and float64 references here, whi
 preconditions -- integer data, sums of |terms| below 2^24, ``small`` references exact in bf16, ``round``
 references with at least 8 exact ties and 64 inexact outputs, tie-rich pool windows with every winner -- on the
 CPU.  The float64 references themselves are anchored to fp32 torch autograd on ``randn`` data, the pool routing to
-autograd of ``max_pool2d``, and ``assert_exact``'s failure report is checked on planted mismatches.
+autograd of ``max_pool2d``, and ``assert_exact``'s failure report is checked on planted mismatches.  The block
+references (tests/test_exact_blocks.py's tables) get the same two checks: preconditions in every regime used, and,
+with rounding switched off, agreement with fp32 autograd of the same modules to 1e-5.
 """
 import pytest
 import torch
 import torch.nn.functional as F
 
 import exact_data as E
+import test_exact_blocks as TB
 import test_exact_conv as TC
 import test_exact_fp32 as TF
 import test_exact_pool as TP
@@ -105,6 +108,41 @@ def test_fp32_case_tables_meet_their_preconditions():
         E.f32_deconv_case(*_shape(case))
 
 
+def test_block_case_tables_meet_their_preconditions():
+    """Every case of tests/test_exact_blocks.py, in the regime it is used in: the builders assert integers, every
+    forward / dgrad / weight-gradient sum of |terms| below 2^24, ``small`` stored tensors exact in bf16, ``round``
+    outputs with ties and inexact values, live ReLUs and non-trivial gradients."""
+    for case in TB.ENC_CASES:
+        c = TB.enc_case(case)
+        assert (c.dx is None) == (case[1] == 0) and (c.code is None) == bool(c.x.shape[2] % 2 or c.x.shape[3] % 2)
+        assert float((c.dskip.abs() + E.pool_route(c.dpooled.abs(), c.q, *c.y.shape[2:])).max()) <= 128   # exact in bf16
+    for case in TB.MID_CASES:
+        c = TB.mid_case(case)
+        assert torch.equal(c.g, c.g * (c.y > 0)) and bool((c.g != 0).any())
+    for case in TB.DEC_CASES:
+        c = TB.dec_case(case)
+        if case[7]:
+            (Hs, Ws), (top, left) = case[7], c.crop
+            assert tuple(c.dskip.shape[2:]) == (Hs, Ws) and (top, left) == E.crop_offsets(Hs, Ws, *c.y.shape[2:])
+            win = torch.zeros_like(c.dskip)
+            win[:, :, top:top + c.y.shape[2], left:left + c.y.shape[3]] = 1
+            assert not bool((c.dskip * (1 - win)).any()) and bool((c.dskip * win).any())
+    for case in TB.HALF_CASES:
+        TB.half_case(case)
+    for case in TB.DEFER_CASES:
+        c = TB.defer_case(case)
+        assert c.x.shape[0] == sum(TB.DEFER_SIZES) and c.dx is not None
+    small, rnd = E.trunk_case("small", *TB.TRUNK), E.trunk_case("round", *TB.TRUNK)
+    assert len(small.G) == 46 and torch.equal(small.G["segmap.bias"], small.G0["segmap.bias"])
+    assert max(float(t.abs().max()) for t in small.stored.values()) <= 256
+    assert max(float(t.abs().max()) for t in rnd.stored.values()) > 256
+    # every regime a block kind is used in rounds where it says it does
+    for c in (TB.enc_case(TB.ENC_CASES[6]), TB.mid_case(TB.MID_CASES[1]), TB.dec_case(TB.DEC_CASES[6])):
+        assert E.rounding_census(c.raw.a)[1] >= 64 and E.rounding_census(c.raw.y)[0] >= 8
+        assert E.rounding_census(c.raw.g1)[1] >= 64, "the stored gradient between the two convs must round"
+        assert not torch.equal(E.bf16(c.raw.dx).double(), c.raw.dx)
+
+
 def _close(a, b, tol):
     return ((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30)).item() < tol
 
@@ -189,3 +227,79 @@ def test_guarded_buffers_detect_overruns_on_the_cpu():
     Fl.buf[64 + 5] = 0.0
     with pytest.raises(AssertionError):
         Fl.check("flat overrun")
+
+
+def _randn_double_conv(g, cin, cmid, cout):
+    return (torch.randn(cmid, cin, 3, 3, generator=g), torch.randn(cmid, generator=g),
+            torch.randn(cout, cmid, 3, 3, generator=g), torch.randn(cout, generator=g))
+
+
+def _leaves(*ts):
+    return [t.clone().requires_grad_(True) for t in ts]
+
+
+def test_block_references_match_fp32_autograd_on_randn():
+    """The float64 block references with every rounding switched off against plain fp32 autograd of the same
+    modules (conv -> ReLU -> conv -> ReLU, max-pool, ConvTranspose2d + centre crop + cat), to 1e-5 relative: the
+    masking conventions of the engines are then the only thing the references add."""
+    g = E.rng(5)
+    D = lambda *ts: [t.double() for t in ts]   # noqa: E731
+    # encoder block 5 -> 6 at 6 x 7 (odd width: the last column is outside the pooled area)
+    x = torch.randn(2, 5, 6, 7, generator=g)
+    P = _randn_double_conv(g, 5, 6, 6)
+    dskip, dpooled = torch.randn(2, 6, 6, 7, generator=g), torch.randn(2, 6, 3, 3, generator=g)
+    xl, *pl = _leaves(x, *P)
+    y = F.relu(F.conv2d(F.relu(F.conv2d(xl, pl[0], pl[1], padding=1)), pl[2], pl[3], padding=1))
+    pooled = F.max_pool2d(y, 2, 2)
+    grads = torch.autograd.grad([y, pooled], [xl] + pl, [dskip, dpooled], retain_graph=True)
+    r = E.enc_block_ref(*D(x, *P, dskip, dpooled), rnd=False)
+    assert _close(r.y, y, 1e-5) and _close(r.pooled, pooled, 1e-5)
+    for got, ref in zip((r.dx, r.dw1, r.db1, r.dw2, r.db2), grads):
+        assert _close(got, ref, 1e-5)
+    # DoubleConv from an already-masked output gradient
+    gy = torch.randn(2, 6, 6, 7, generator=g)
+    a64, y64 = E.double_conv_fwd_ref(*D(x, *P), rnd=False)
+    r = E.double_conv_bwd_ref(x.double(), a64, P[0].double(), P[2].double(), gy.double() * (y64 > 0), rnd=False)
+    grads = torch.autograd.grad(y, [xl] + pl, gy)
+    for got, ref in zip((r.dx, r.dw1, r.db1, r.dw2, r.db2), grads):
+        assert _close(got, ref, 1e-5)
+    # decoder block 8 -> 4 with an 8 x 13 skip cropped to 6 x 10 at (1, 2); x is a ReLU output (dx masked by x > 0)
+    x0, skip = torch.randn(2, 8, 3, 5, generator=g), torch.randn(2, 4, 8, 13, generator=g)
+    wt, bt = torch.randn(8, 4, 2, 2, generator=g), torch.randn(4, generator=g)
+    P = _randn_double_conv(g, 8, 4, 4)
+    gy = torch.randn(2, 4, 6, 10, generator=g)
+    x0l, sl, wtl, btl, *pl = _leaves(x0, skip, wt, bt, *P)
+    up = F.conv_transpose2d(F.relu(x0l), wtl, btl, stride=2)
+    top, left = E.crop_offsets(8, 13, 6, 10)
+    assert (top, left) == (1, 2) and E.crop_offsets(7, 11, 6, 10) == (0, 0)           # Python rounds 1.5 and 0.5 to even
+    cat = torch.cat([sl[:, :, top:top + 6, left:left + 10], up], 1)
+    y = F.relu(F.conv2d(F.relu(F.conv2d(cat, pl[0], pl[1], padding=1)), pl[2], pl[3], padding=1))
+    grads = torch.autograd.grad(y, [x0l, sl, wtl, btl] + pl, gy)
+    r = E.dec_block_ref(*D(F.relu(x0), skip, wt, bt, *P, gy), rnd=False)
+    assert _close(r.y, y, 1e-5)
+    for got, ref in zip((r.dx, r.dskip, r.dwt, r.dbt, r.dw1, r.db1, r.dw2, r.db2), grads):
+        assert _close(got, ref, 1e-5)
+    assert not bool(r.dskip[:, :, 0].any()) and not bool(r.dskip[:, :, 7:].any()) and not bool(r.dskip[:, :, :, :2].any()) \
+        and not bool(r.dskip[:, :, :, 12:].any()) and bool(r.dskip[:, :, 1:7, 2:12].any())
+
+
+def test_trunk_reference_matches_fp32_autograd_of_the_model():
+    """``trunk_ref`` without rounding against fp32 autograd of the ``unet`` modules themselves (encoder, mid,
+    decoder; no head) on randn parameters: every parameter gradient and the output, to 1e-5 relative."""
+    from distributedpytorch_amd.models.unet import build_model
+    torch.manual_seed(7)
+    net = build_model("unet")
+    g = E.rng(7)
+    img = torch.randn(1, 3, 16, 32, generator=g)
+    x, *skips = net.encoder(img)
+    y = net.decoder(net.mid(x), *skips)
+    gy = torch.randn(y.shape, generator=g)
+    names = [n for n, _ in net.named_parameters() if not n.startswith("segmap")]
+    params = dict(net.named_parameters())
+    assert [p for p, _ in E.trunk_names()] == sorted({n.rsplit(".", 1)[0] for n in names}, key=[p for p, _ in E.trunk_names()].index)
+    grads = torch.autograd.grad(y, [params[n] for n in names], gy)
+    P = {n: params[n].detach().double() for n in names}
+    stored, ref = E.trunk_ref(P, img.double(), gy.double(), rnd=False)
+    assert _close(stored["dec3.y"], y, 1e-5)
+    for n, got in zip(names, grads):
+        assert _close(ref[n], got, 1e-5), n
